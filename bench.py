@@ -2,7 +2,21 @@
 """Throughput of the adversarial train step (utils/trainer.py:run_training, one
 iteration = :426-559) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-graph] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                    [--no-graph] [--no-cpu]
+
+A plain run sets up, warms up, times one region of exactly --steps steps
+(--config trainer / dp1 keep their median of three, see --repeats),
+writes its outputs when --dump-outputs is given and prints the JSON line.
+--full adds everything that takes runs of its own: three timed regions (the
+median is reported) instead of one, the dominant kernel's `roofline` and
+`fp32_equivalent` blocks (kernels re-timed from graphs of their own) and the
+numpy-oracle `cpu_baseline` (--no-cpu leaves that one out of a --full run).
+--dump-outputs DIR writes what the last timed step left with its caller (the
+step's loss vector and logits, every parameter after the update and its
+gradient) as DIR/<name>.npy, float32, after removing the *.npy files an earlier
+run left in DIR; inputs, seeds and the number of steps run are fixed by the
+arguments, so two builds can be compared array for array.
 
 Workload (BASELINE.json configs[2]): PointNetCls(k=40) + DeepConvDiscNet(40,1),
 B=32 labelled + B=32 unlabelled ModelNet40-shaped clouds of N=1024 points per
@@ -62,8 +76,15 @@ def parse():
                          "many consecutive iterations over the resident batch pool; a timed "
                          "region still runs exactly --steps steps (the remainder as one-step "
                          "graphs)")
-    ap.add_argument("--repeats", type=int, default=3,
-                    help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: three timed regions instead "
+                         "of one, the roofline / fp32_equivalent blocks and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (losses, logits, "
+                         "updated parameters, gradients) as DIR/<name>.npy, float32")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported "
+                         "(default: 1; 3 with --full and for --config trainer / dp1)")
     ap.add_argument("--points", type=int, default=1024,
                     help="points per cloud of the adv step (1024: the metric's config; 2048: "
                          "BASELINE configs[4]'s per-rank shape)")
@@ -89,7 +110,72 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher self-test: start the --gpus ranks, form the process group, "
                          "print the JSON world/backend line; no GPU work")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        # trainer / dp1 difference whole runs or alternate forms: their figures are medians
+        args.repeats = 3 if args.full or args.config in ("trainer", "dp1") else 1
+    if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
+    if args.dump_outputs and args.config in ("trainer", "dp1"):
+        ap.error(f"--dump-outputs: --config {args.config} times whole runs, not one step's path")
+    return args
+
+
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
+
+
+def snapshot_outputs(arrays, modules, grads=True):
+    """Host float32 copies of what the last timed step left with its caller:
+    the named device tensors in `arrays` plus, for each (prefix, module), every
+    parameter after the update (<prefix>.<name>) and its gradient
+    (<prefix>.<name>.grad).  Taken right after the timed regions, before
+    anything else runs on those buffers."""
+    out = dict(arrays)
+    for prefix, mod in modules:
+        for name, p in mod.named_parameters():
+            out[f"{prefix}.{name}"] = p
+            if grads and p.grad is not None:
+                out[f"{prefix}.{name}.grad"] = p.grad
+    return {k: v.detach().to("cpu", torch.float32).contiguous().numpy().copy()
+            for k, v in out.items()}
+
+
+def _dump_cap(sizes, budget):
+    """The largest per-array byte cap c with sum(min(size, c)) <= budget, or
+    None when every array fits whole: small arrays are accounted for first and
+    what they leave is shared among the larger ones."""
+    if sum(sizes) <= budget:
+        return None
+    left, todo = budget, sorted(sizes)
+    for k, size in enumerate(todo):
+        cap = left // (len(todo) - k)
+        if size > cap:
+            return cap
+        left -= size
+    return None
+
+
+def dump_outputs(path, snap):
+    """Write a snapshot_outputs() result as path/<name>.npy.  While the arrays
+    and their .npy headers fit DUMP_LIMIT together, every array is written
+    whole with its shape.  Only a larger output is cut: the arrays above the
+    cap _dump_cap() leaves them become flat, fixed seeded samples of their
+    elements (the same ones in every run: they depend on the array's name and
+    size), the smaller arrays stay whole.  *.npy files already in path are
+    removed first, so the folder holds this run's arrays and no others."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    for old in glob.glob(os.path.join(path, "*.npy")):  # an earlier run's arrays, maybe other names
+        os.remove(old)
+    header = 4096  # generous bound on one .npy header
+    cap = _dump_cap([a.nbytes for a in snap.values()], DUMP_LIMIT - header * len(snap))
+    for name in sorted(snap):
+        a = snap[name]
+        if cap is not None and a.nbytes > cap:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(a.size, size=max(1, cap // a.itemsize), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _free_port():
@@ -539,12 +625,17 @@ def bench_cls(args):
     dt = float(np.median(regions))
     gflop = 11.18  # algorithmic FLOPs of one cfg-2 step
     loss = float(step.losses[0].item())
-    fw = [model.feat.conv1.weight, model.feat.conv1.bias, model.feat.conv2.weight,
-          model.feat.conv2.bias, model.feat.conv3.weight, model.feat.conv3.bias,
-          model.feat.conv4.weight, model.feat.conv4.bias]
-    roof = feat_roofline(pool[(args.steps - 1) % POOL][0], fw, prec,
-                         "r*_cls_pmc_traffic.json" if prec == "bf16" else None,
-                         "cls" if prec == "bf16" else None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, snapshot_outputs(
+            {"losses": step.losses, "logits": step.logits}, [("G", model)]))
+    roof = None
+    if args.full:
+        fw = [model.feat.conv1.weight, model.feat.conv1.bias, model.feat.conv2.weight,
+              model.feat.conv2.bias, model.feat.conv3.weight, model.feat.conv3.bias,
+              model.feat.conv4.weight, model.feat.conv4.bias]
+        roof = feat_roofline(pool[(args.steps - 1) % POOL][0], fw, prec,
+                             "r*_cls_pmc_traffic.json" if prec == "bf16" else None,
+                             "cls" if prec == "bf16" else None)
     out = {
         "metric": "point-clouds/sec (cls train step, no discriminator), B=32 N=1024 ModelNet40, 1 GPU",
         "value": round(B * args.steps / dt, 1), "unit": "clouds/s", "n_gpus": 1,
@@ -559,12 +650,13 @@ def bench_cls(args):
                                "N=1024 (BASELINE configs[1])", "global_batch": B, "points": N,
                    "parallelism": "dp1", "hip_graph": True, "steps_per_graph": G, "precision": prec},
         "timing": {"regions_s": [round(r, 6) for r in regions], "reported": "median"},
-        "roofline": roof,
         "step_flops": {"gflop_per_step": gflop,
                        "achieved_tflops": round(gflop * args.steps / dt / 1e3, 2)},
         "loss_last_step": round(loss, 5), "finite": bool(np.isfinite(loss)),
     }
-    if not args.no_cpu:
+    if roof is not None:
+        out["roofline"] = roof
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_cls(args.cpu_seconds)
     print(json.dumps(_with_runtime(out)), flush=True)
 
@@ -662,6 +754,11 @@ def bench_cls_ft(args):
     regions = timed_regions(one, args.steps, args.repeats)
     dt = float(np.median(regions))
     loss = loss_now(args.steps - 1)
+    if args.dump_outputs:
+        last = (step.losses if not args.ft_body else losses[(args.steps - 1) % POOL].view(1))
+        # --ft-body: each graph owns its gradient buffers, p.grad is the last captured one's
+        dump_outputs(args.dump_outputs, snapshot_outputs({"losses": last}, [("G", model)],
+                                                         grads=not args.ft_body))
     out = {
         "metric": "point-clouds/sec (cls train step with feature_transform=True), B=32 N=1024 "
                   "ModelNet40, 1 GPU",
@@ -678,8 +775,9 @@ def bench_cls_ft(args):
     }
     if why:
         out["graph_capture_error"] = why
-    out["roofline"] = ft_roofline(B)
-    if not args.no_cpu:
+    if args.full:
+        out["roofline"] = ft_roofline(B)
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_ft(args.cpu_seconds, adversarial=False)
     print(json.dumps(_with_runtime(out)), flush=True)
 
@@ -767,6 +865,10 @@ def bench_adv_ft(args):
     regions = timed_regions(one, args.steps, args.repeats)
     dt = float(np.median(regions))
     vals = [float(v) for v in step.losses[:4].cpu()]
+    if args.dump_outputs:
+        # --ft-body: each graph owns its gradient buffers, p.grad is the last captured one's
+        dump_outputs(args.dump_outputs, snapshot_outputs(
+            {"losses": step.losses}, [("G", model), ("D", model_D)], grads=not args.ft_body))
     out = {
         "metric": "point-clouds/sec (adversarial train step, generator with feature_transform=True), "
                   "B=32+32 N=1024 ModelNet40, 1 GPU",
@@ -787,14 +889,15 @@ def bench_adv_ft(args):
     # the dominant kernel: the 1024-channel conv + max, twice per generator pass
     # (over the 2B clouds of both batches in the fused step, B in the body)
     C = B if args.ft_body else 2 * B
-    roof = ft_roofline(C)
-    if not args.ft_body:
+    roof = ft_roofline(C) if args.full else None
+    if roof is not None and not args.ft_body:
         roof["traffic"], roof["traffic_source"] = _pmc_traffic(
             "r*_adv_ft_pmc_traffic.json", ["pcadv::k_conv4_max"])
         roof["traffic_unit"] = "bytes/launch (L2->memory, PMC FETCH_SIZEx2+WRITE_SIZE)"
         roof["mfma_busy"], roof["mfma_busy_source"] = _pmc_mfma("adv_ft", "k_conv4_max")
-    out["roofline"] = roof
-    if not args.no_cpu:
+    if roof is not None:
+        out["roofline"] = roof
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_ft(args.cpu_seconds, adversarial=True)
     print(json.dumps(_with_runtime(out)), flush=True)
 
@@ -933,64 +1036,86 @@ def bench_seg(args):
     dense_bwd = 2 * (per_pt_fwd - 512 * 2048) - 3 * 64
     gflop = 2.0 * Bs * Ns * (per_pt_fwd + dense_bwd) / 1e9
     loss = float(step.loss.item())
-    # dominant kernel: conv6 + ReLU + max over points as the step runs it
-    # (pcadv_conv_max_bf2: the screened GEMM k_gemm_bf2_big<2> (256x256 tiles) on the bf16 planes
-    # conv5's epilogue wrote + the exact re-evaluation k_max_combine), timed with
-    # HIP events on the current stream over the last batch's x5
-    from adversarial_learning_on_pointclouds_amd import seg as segmod
-    from adversarial_learning_on_pointclouds_amd._lib import check, stream_ptr
-    import ctypes
-    params = [p for p in model.parameters()]
-    segmod._engine().split(step.param, step.wph, step.wpl)
-    fw = segmod.seg_forward(pool[(args.steps - 1) % 2][0], pool[(args.steps - 1) % 2][1], params,
-                            wplanes=step.wplanes, precision=precision)
-    lib = segmod._engine().lib
-    gmax = torch.empty(Bs, 2048, device=dev)
-    gidx = torch.empty(Bs, 2048, device=dev, dtype=torch.int32)
-    wsb = lib.pcadv_conv_max_x3_workspace_bytes(Bs, Ns, 2048)
-    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
-    W6 = fw["W"][5]
-    b6 = params[11]
-    x5 = ctypes.c_void_p(fw["xloc"].data_ptr() + 4 * segmod._OFF[4])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, snapshot_outputs({"losses": step.loss.view(1)},
+                                                         [("model", model)]))
 
-    x5p, w6p = fw["x5p"], fw["W6p"]
-    big = os.environ.get("PCADV_GEMM_BIG", "1") != "0"
-    glds = os.environ.get("PCADV_GEMM_GLDS", "1") != "0"
-    gname = (f"k_gemm_bf2_big<2, {'true' if glds else 'false'}> (operands staged by "
-             f"{'LDS-DMA' if glds else 'registers'})") if big else "k_gemm_x3<2,2,2,3>"
-    kname = f"pcadv_conv_max_bf2: {gname}" if x5p is not None else "pcadv_conv_max_x3: k_gemm_x3<0,0,2,3>"
+    def seg_roofline():
+        # dominant kernel: conv6 + ReLU + max over points as the step runs it
+        # (pcadv_conv_max_bf2: the screened GEMM k_gemm_bf2_big<2> (256x256 tiles) on the bf16 planes
+        # conv5's epilogue wrote + the exact re-evaluation k_max_combine), timed with
+        # HIP events on the current stream over the last batch's x5
+        from adversarial_learning_on_pointclouds_amd import seg as segmod
+        from adversarial_learning_on_pointclouds_amd._lib import check, stream_ptr
+        import ctypes
+        params = [p for p in model.parameters()]
+        segmod._engine().split(step.param, step.wph, step.wpl)
+        fw = segmod.seg_forward(pool[(args.steps - 1) % 2][0], pool[(args.steps - 1) % 2][1], params,
+                                wplanes=step.wplanes, precision=precision)
+        lib = segmod._engine().lib
+        gmax = torch.empty(Bs, 2048, device=dev)
+        gidx = torch.empty(Bs, 2048, device=dev, dtype=torch.int32)
+        wsb = lib.pcadv_conv_max_x3_workspace_bytes(Bs, Ns, 2048)
+        ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+        W6 = fw["W"][5]
+        b6 = params[11]
+        x5 = ctypes.c_void_p(fw["xloc"].data_ptr() + 4 * segmod._OFF[4])
 
-    def cmx():
-        if x5p is not None:
-            (hi, lo), ld, off = x5p
-            check(lib.pcadv_conv_max_bf2(x5, segmod._LOC, segmod._pb(hi, off), segmod._pb(lo, off),
-                                         ld, Bs, Ns, 512,
-                                         ctypes.c_void_p(W6.data_ptr()), segmod._pb(w6p[0]),
-                                         segmod._pb(w6p[1]), ctypes.c_void_p(b6.data_ptr()), 2048, 1,
-                                         ctypes.c_void_p(gmax.data_ptr()), ctypes.c_void_p(gidx.data_ptr()),
-                                         ctypes.c_void_p(ws.data_ptr()), wsb, stream_ptr()), "conv_max_bf2")
-            return
-        check(lib.pcadv_conv_max_x3(x5, segmod._LOC, Bs, Ns, 512, ctypes.c_void_p(W6.data_ptr()),
-                                    ctypes.c_void_p(b6.data_ptr()), 2048, 1,
-                                    ctypes.c_void_p(gmax.data_ptr()), ctypes.c_void_p(gidx.data_ptr()),
-                                    ctypes.c_void_p(ws.data_ptr()), wsb, stream_ptr()), "conv_max_x3")
-    for _ in range(3):
-        cmx()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = 20
-    ev0.record()
-    for _ in range(reps):
-        cmx()
-    ev1.record()
-    torch.cuda.synchronize()
-    kern_s = ev0.elapsed_time(ev1) / 1e3 / reps
-    kflops = 2.0 * Bs * Ns * 512 * 2048
-    kissued = 3 * kflops  # three bf16 MFMA products per f32 product (hi/lo splits)
-    busy, busy_src = _pmc_mfma("seg", "k_gemm_bf2_big<2" if big else "k_gemm_x3<2, 2, 2, 3>") \
-        if precision == "fp32" else (None, None)
-    traffic, traffic_src = _pmc_traffic(
-        "r*_seg_pmc_traffic.json",
-        ("pcadv::k_gemm_bf2_big<2" if big else "pcadv::k_gemm_x3<2, 2, 2, 3>", "pcadv::k_max_combine"))
+        x5p, w6p = fw["x5p"], fw["W6p"]
+        big = os.environ.get("PCADV_GEMM_BIG", "1") != "0"
+        glds = os.environ.get("PCADV_GEMM_GLDS", "1") != "0"
+        gname = (f"k_gemm_bf2_big<2, {'true' if glds else 'false'}> (operands staged by "
+                 f"{'LDS-DMA' if glds else 'registers'})") if big else "k_gemm_x3<2,2,2,3>"
+        kname = f"pcadv_conv_max_bf2: {gname}" if x5p is not None else "pcadv_conv_max_x3: k_gemm_x3<0,0,2,3>"
+
+        def cmx():
+            if x5p is not None:
+                (hi, lo), ld, off = x5p
+                check(lib.pcadv_conv_max_bf2(x5, segmod._LOC, segmod._pb(hi, off), segmod._pb(lo, off),
+                                             ld, Bs, Ns, 512,
+                                             ctypes.c_void_p(W6.data_ptr()), segmod._pb(w6p[0]),
+                                             segmod._pb(w6p[1]), ctypes.c_void_p(b6.data_ptr()), 2048, 1,
+                                             ctypes.c_void_p(gmax.data_ptr()), ctypes.c_void_p(gidx.data_ptr()),
+                                             ctypes.c_void_p(ws.data_ptr()), wsb, stream_ptr()), "conv_max_bf2")
+                return
+            check(lib.pcadv_conv_max_x3(x5, segmod._LOC, Bs, Ns, 512, ctypes.c_void_p(W6.data_ptr()),
+                                        ctypes.c_void_p(b6.data_ptr()), 2048, 1,
+                                        ctypes.c_void_p(gmax.data_ptr()), ctypes.c_void_p(gidx.data_ptr()),
+                                        ctypes.c_void_p(ws.data_ptr()), wsb, stream_ptr()), "conv_max_x3")
+        for _ in range(3):
+            cmx()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 20
+        ev0.record()
+        for _ in range(reps):
+            cmx()
+        ev1.record()
+        torch.cuda.synchronize()
+        kern_s = ev0.elapsed_time(ev1) / 1e3 / reps
+        kflops = 2.0 * Bs * Ns * 512 * 2048
+        kissued = 3 * kflops  # three bf16 MFMA products per f32 product (hi/lo splits)
+        busy, busy_src = _pmc_mfma("seg", "k_gemm_bf2_big<2" if big else "k_gemm_x3<2, 2, 2, 3>") \
+            if precision == "fp32" else (None, None)
+        traffic, traffic_src = _pmc_traffic(
+            "r*_seg_pmc_traffic.json",
+            ("pcadv::k_gemm_bf2_big<2" if big else "pcadv::k_gemm_x3<2, 2, 2, 3>", "pcadv::k_max_combine"))
+        return {"bound": "mfma",
+                "kernel": kname + " (conv6 512->2048 screened top-2 per 128-point tile) "
+                          "+ k_max_combine (exact f32 re-evaluation)",
+                "achieved": round(kflops / kern_s / 1e12, 2), "peak": BF16_PEAK,
+                "unit": "TFLOP/s", "frac": round(kflops / kern_s / 1e12 / BF16_PEAK, 4),
+                "issued_frac": round(kissued / kern_s / 1e12 / BF16_PEAK, 4),
+                "traffic": traffic,
+                "traffic_unit": "bytes/launch (L2->memory, PMC FETCH_SIZEx2+WRITE_SIZE)",
+                "traffic_source": traffic_src, "avg_launch_us": round(kern_s * 1e6, 2),
+                "mfma_busy": busy, "mfma_busy_source": busy_src,
+                "algorithmic_flops_per_launch": kflops,
+                "algorithmic_bytes_per_launch": Bs * Ns * 512 * 4 + 2048 * 512 * 4 + Bs * 2048 * 8,
+                "issued_bf16_flops_per_launch": kissued,
+                "peak_basis": "dense bf16 MFMA 2500 TF, the pipe the kernel runs on; achieved = "
+                              "algorithmic f32 FLOPs / launch time (issued_frac: the three "
+                              "bf16 split products per f32 product)"}
+
     out = {
         "metric": "point-clouds/sec (seg train step), B=16 N=2048 ShapeNet-part, 1 GPU",
         "value": round(Bs * args.steps / dt, 1), "unit": "clouds/s", "n_gpus": 1,
@@ -1007,27 +1132,13 @@ def bench_seg(args):
                                "(BASELINE configs[3])", "global_batch": Bs, "points": Ns,
                    "parallelism": "dp1", "hip_graph": True},
         "timing": {"regions_s": [round(r, 6) for r in regions], "reported": "median"},
-        "roofline": {"bound": "mfma",
-                     "kernel": kname + " (conv6 512->2048 screened top-2 per 128-point tile) "
-                               "+ k_max_combine (exact f32 re-evaluation)",
-                     "achieved": round(kflops / kern_s / 1e12, 2), "peak": BF16_PEAK,
-                     "unit": "TFLOP/s", "frac": round(kflops / kern_s / 1e12 / BF16_PEAK, 4),
-                     "issued_frac": round(kissued / kern_s / 1e12 / BF16_PEAK, 4),
-                     "traffic": traffic,
-                     "traffic_unit": "bytes/launch (L2->memory, PMC FETCH_SIZEx2+WRITE_SIZE)",
-                     "traffic_source": traffic_src, "avg_launch_us": round(kern_s * 1e6, 2),
-                     "mfma_busy": busy, "mfma_busy_source": busy_src,
-                     "algorithmic_flops_per_launch": kflops,
-                     "algorithmic_bytes_per_launch": Bs * Ns * 512 * 4 + 2048 * 512 * 4 + Bs * 2048 * 8,
-                     "issued_bf16_flops_per_launch": kissued,
-                     "peak_basis": "dense bf16 MFMA 2500 TF, the pipe the kernel runs on; achieved = "
-                                   "algorithmic f32 FLOPs / launch time (issued_frac: the three "
-                                   "bf16 split products per f32 product)"},
         "step_flops": {"gflop_per_step": round(gflop, 2),
                        "achieved_tflops": round(gflop * args.steps / dt / 1e3, 2)},
         "loss_last_step": round(loss, 5), "finite": bool(np.isfinite(loss)),
     }
-    if not args.no_cpu:
+    if args.full:
+        out["roofline"] = seg_roofline()
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_seg(args.cpu_seconds, Bs, Ns)
     print(json.dumps(_with_runtime(out)), flush=True)
 
@@ -1201,19 +1312,23 @@ def main():
     dt = float(np.median(regions))
     losses = step.losses[:4].cpu().numpy().tolist()
     finite = all(np.isfinite(losses))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, snapshot_outputs(
+            {"losses": step.losses, "logits": step.logits}, [("G", model), ("D", model_D)]))
 
-    # dominant kernel k_conv4_max and the feature forward pair, timed with HIP
-    # events over the last resident batch (the step's 2B clouds)
-    pg, lab, pn = pool[(args.steps - 1) % POOL]
-    pts_all = torch.cat([pg, pn], 0).contiguous()
-    fw = [model.feat.conv1.weight, model.feat.conv1.bias, model.feat.conv2.weight,
-          model.feat.conv2.bias, model.feat.conv3.weight, model.feat.conv3.bias,
-          model.feat.conv4.weight, model.feat.conv4.bias]
-    # the committed PMC passes ran the default workload (fp32, N = 1024)
-    roof = feat_roofline(pts_all, fw, adv_prec,
-                         "r*_pmc_traffic.json" if (N == 1024 and adv_prec == "fp32") else None,
-                         "adv" if (N == 1024 and adv_prec == "fp32") else None)
-    pair = roof["pair"]
+    roof = None
+    if args.full:
+        # dominant kernel k_conv4_max and the feature forward pair, timed with HIP
+        # events over the last resident batch (the step's 2B clouds)
+        pg, lab, pn = pool[(args.steps - 1) % POOL]
+        pts_all = torch.cat([pg, pn], 0).contiguous()
+        fw = [model.feat.conv1.weight, model.feat.conv1.bias, model.feat.conv2.weight,
+              model.feat.conv2.bias, model.feat.conv3.weight, model.feat.conv3.bias,
+              model.feat.conv4.weight, model.feat.conv4.bias]
+        # the committed PMC passes ran the default workload (fp32, N = 1024)
+        roof = feat_roofline(pts_all, fw, adv_prec,
+                             "r*_pmc_traffic.json" if (N == 1024 and adv_prec == "fp32") else None,
+                             "adv" if (N == 1024 and adv_prec == "fp32") else None)
     # algorithmic FLOPs of one B=32 adversarial step (44.53 at N=2048)
     step_gflop = 22.47 if N == 1024 else 22.47 * N / 1024.0
     step_tf = step_gflop * world * args.steps / dt / 1e3
@@ -1242,18 +1357,19 @@ def main():
         "backend": ((_backend() if _backend() != "nccl" else "nccl (RCCL)") if world > 1 else None),
         "timing": {"regions_s": [round(r, 6) for r in regions], "reported": "median",
                    "per_region": "barrier + synchronize on both sides, max over ranks"},
-        "roofline": roof,
-        "fp32_equivalent": {
-            "kernel": "feature forward pair (conv1..conv4 + max)",
-            "achieved_tflops": pair["achieved"], "f32_mfma_peak_tflops": F32_PEAK,
-            "note": "algorithmic f32 FLOPs / time against the f32 MFMA peak; the f32 products are "
-                    "emulated on the bf16 pipe (split operands, f32 accumulate, winners "
-                    "re-evaluated in exact f32), so this is not a roofline fraction"},
         "step_flops": {"gflop_per_step": step_gflop, "achieved_tflops": round(step_tf, 2)},
         "losses_last_step": [round(v, 5) for v in losses],
         "finite": finite,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if roof is not None:
+        result["roofline"] = roof
+        result["fp32_equivalent"] = {
+            "kernel": "feature forward pair (conv1..conv4 + max)",
+            "achieved_tflops": roof["pair"]["achieved"], "f32_mfma_peak_tflops": F32_PEAK,
+            "note": "algorithmic f32 FLOPs / time against the f32 MFMA peak; the f32 products are "
+                    "emulated on the bf16 pipe (split operands, f32 accumulate, winners "
+                    "re-evaluated in exact f32), so this is not a roofline fraction"}
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     if rank == 0:
         print(json.dumps(_with_runtime(result)), flush=True)

@@ -39,13 +39,13 @@ if [ "$part" = A ]; then
   prof _adv_ft --config adv_ft --steps 20 --warmup 5
 fi
 if [ "$part" = B ]; then
-  step bench 300 python bench.py
-  step bench_cls 300 python bench.py --config cls
-  step bench_seg 300 python bench.py --config seg --steps 20 --warmup 3
-  step bench_n2048 300 python bench.py --points 2048 --no-cpu --steps 100 --warmup 10
+  step bench 300 python bench.py --full
+  step bench_cls 300 python bench.py --full --config cls
+  step bench_seg 300 python bench.py --full --config seg --steps 20 --warmup 3
+  step bench_n2048 300 python bench.py --full --points 2048 --no-cpu --steps 100 --warmup 10
   step bench_trainer 300 python bench.py --config trainer --steps 300 --warmup 20
-  step bench_cls_ft 300 python bench.py --config cls_ft --steps 100 --warmup 10
-  step bench_adv_ft 300 python bench.py --config adv_ft --steps 100 --warmup 10
+  step bench_cls_ft 300 python bench.py --full --config cls_ft --steps 100 --warmup 10
+  step bench_adv_ft 300 python bench.py --full --config adv_ft --steps 100 --warmup 10
   for i in 1 2 3; do
     step driver_cmd_$i 300 python bench.py --gpus 1 --steps 20 --warmup 5
   done

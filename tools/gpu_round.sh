@@ -38,14 +38,14 @@ if [ "$only" = all ] || [ "$only" = bench ]; then
   python tools/pmc_traffic.py "gpurun_out/${tag}_pmc_fetch_cls" "gpurun_out/${tag}_pmc_write_cls" "profiles/${tag}_cls_pmc_traffic.json" > /dev/null
   prof _seg --config seg --steps 5 --warmup 1
   python tools/pmc_traffic.py "gpurun_out/${tag}_pmc_fetch_seg" "gpurun_out/${tag}_pmc_write_seg" "profiles/${tag}_seg_pmc_traffic.json" > /dev/null
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
   grep '"metric"' "gpurun_out/${tag}_bench.log"
-  step bench_cls 600 python bench.py --config cls
-  step bench_seg 600 python bench.py --config seg --steps 20 --warmup 3
-  step bench_n2048 600 python bench.py --points 2048 --no-cpu --steps 100 --warmup 10
+  step bench_cls 600 python bench.py --full --config cls
+  step bench_seg 600 python bench.py --full --config seg --steps 20 --warmup 3
+  step bench_n2048 600 python bench.py --full --points 2048 --no-cpu --steps 100 --warmup 10
   step bench_trainer 600 python bench.py --config trainer --steps 300 --warmup 20
-  step bench_cls_ft 600 python bench.py --config cls_ft --steps 100 --warmup 10
-  step bench_adv_ft 600 python bench.py --config adv_ft --steps 100 --warmup 10
+  step bench_cls_ft 600 python bench.py --full --config cls_ft --steps 100 --warmup 10
+  step bench_adv_ft 600 python bench.py --full --config adv_ft --steps 100 --warmup 10
 fi
 if [ "$only" = all ] || [ "$only" = mfma ]; then
   bash tools/gpu_mfma.sh "$tag" || exit 1

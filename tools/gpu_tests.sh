@@ -17,4 +17,4 @@ step() {  # step <name> <seconds> <cmd...>
 }
 step pytest_gpu 1000 python -u -m pytest tests -m gpu -v --timeout 180 --timeout-method thread -rf
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 300 python bench.py --steps 50 --warmup 10 --cpu-seconds 5
+step bench 300 python bench.py --full --steps 50 --warmup 10 --cpu-seconds 5
