@@ -7,7 +7,7 @@
 //                   be one matrix per cloud in either layout, so the same kernel
 //                   runs the per-cloud transform x2 . T (bmm).
 //   k_pw_bwd_data   dx = (dy * act'(y)) w, optionally accumulated into dx
-//   k_pw_bwd_weight per-256-row partial dW / db slabs (one group = all rows, or
+//   k_pw_bwd_weight per-128-row partial dW / db slabs (one group = all rows, or
 //                   one cloud for dT), then k_pw_reduce sums the slabs in order
 //   k_convmax_bwd   sparse backward of conv + max over points (optionally with
 //                   the ReLU before the max): dW/db by gathering the argmax rows,
@@ -857,7 +857,8 @@ k_convmax_bwd(const float* __restrict__ dg, const int32_t* __restrict__ gidx,
 
 // ---------------------------------------------------------------------------
 // feature_transform_regularizer: ||T T^T - I||_F per cloud and its gradient
-// (2 * gscale / (B n_b)) (T T^T - I) T, stored or (accumulate) added into dT;
+// (2 * gscale / (B n_b)) (T T^T - I) T (0 where n_b = 0), stored or
+// (accumulate) added into dT;
 // norms (nullable) written in either mode; step_inc (nullable): block 0 also
 // advances the step counter (the fused cls FT step's, ahead of its Adam)
 // ---------------------------------------------------------------------------
@@ -919,7 +920,10 @@ k_tnet_reg(const float* __restrict__ T, int B, int k, float* __restrict__ norms,
   if (norms && tid == 0) norms[b] = n;
   if (step_inc && b == 0 && tid == 0) *step_inc += 1;
   if (!dT) return;
-  const float scale = 2.f * (*gscale) / ((float)B * n);
+  // n == 0 (T T^T = I exactly: an STNkd whose fc3 is zero, a signed
+  // permutation): the zero gradient, as torch.norm's backward, not inf * 0
+  const float scale = n > 0.f ? 2.f * (*gscale) / ((float)B * n) : 0.f;
+  if (accumulate && n == 0.f) return;  // nothing to add: dT keeps its bits (a -0.f too)
   if (k == 64) {  // (T T^T - I) T in 4 x 4 blocks
     const int i0 = 4 * (tid >> 4), j0 = 4 * (tid & 15);
     float v[4][4] = {};

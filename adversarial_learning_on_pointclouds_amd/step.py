@@ -969,21 +969,23 @@ class ClsFtTrainStep(ClsTrainStep):
         self._pre()
         act = _ft_extractor_forward(P, pts, N)
         # fc1 .. CE and back to dL/dgmax: the cls step's head (part 3); its
-        # dropout draws read the step count of the completed steps
+        # dropout draws read the count of the completed calls (the regulariser
+        # launch below advances it afterwards, with or without Adam)
         dgmax = self.dgmax[:B]
         a.feat_gmax, a.feat_dgmax = act["gmax"].data_ptr(), dgmax.data_ptr()
         self._keep_last = (a, act["gmax"])
         check(self.lib.pcadv_cls_step(ctypes.byref(a), stream_ptr()), "pcadv_cls_step (part 3)")
         # loss += lambda_regu * ||T T^T - I||_F mean (trainer.py:259-266): its
         # value into losses[1], lambda_regu times its gradient added into the
-        # bmm's dT, and (with Adam) the step count advanced, in one launch + the mean
+        # bmm's dT, and the step count advanced (on every call: a grads-only call
+        # draws fresh dropout masks too), in one launch + the mean
         T = act["T"]
 
         def regulariser(dT):
             check(self.lib.pcadv_tnet_reg_step(
                 T.data_ptr(), B, 64, self._norms.data_ptr(), self.losses.data_ptr() + 4,
                 self._lregu.data_ptr(), dT.data_ptr(),
-                self.step_count.data_ptr() if apply_adam else None, stream_ptr()),
+                self.step_count.data_ptr(), stream_ptr()),
                 "pcadv_tnet_reg_step")
         _ft_extractor_backward(P, Gr, act, pts, dgmax, N, dT_hook=regulariser)
         if apply_adam:  # optimizer.step() at the count advanced above

@@ -188,10 +188,10 @@ int pcadv_pw_bwd_data(const float* dy, const float* y, int act, int M, int O, co
                       hipStream_t stream);
 
 /* dW = sum over rows of (dy * act'(y))^T x and db (NULL: skipped), per group
- * of rows_per_group rows (0: all rows; a multiple of 256 dividing M): dw holds
+ * of rows_per_group rows (0: all rows; a multiple of 128 dividing M): dw holds
  * M / rows_per_group matrices, [O][K] or with dw_kmajor=1 [K][O] (dT of the
- * bmm).  O in {64, 128}, K in {3, 64, 128}.  Deterministic (fixed-order
- * reduction over 256-row slabs in the workspace). */
+ * bmm).  O in {64, 128}, K in {3, 64, 128} (K = 3: O = 64, [O][K]).
+ * Deterministic (fixed-order reduction over 128-row slabs in the workspace). */
 size_t pcadv_pw_bwd_weight_workspace_bytes(int M, int O, int K);
 int pcadv_pw_bwd_weight(const float* dy, const float* y, int act, const float* x, int M, int O,
                         int K, int rows_per_group, int dw_kmajor, float* dw, float* db,
@@ -225,15 +225,17 @@ int pcadv_conv_max_bwd(const float* dgmax, const int32_t* gidx, const float* gma
 
 /* feature_transform_regularizer (pointnet.py:345-353): norms[b] =
  * ||T_b T_b^T - I||_F and *reg = mean_b norms[b]; backward dT = *grad_reg *
- * (2 / (B norms[b])) (T T^T - I) T.  k <= 64. */
+ * (2 / (B norms[b])) (T T^T - I) T, and 0 for a cloud with norms[b] = 0 (as
+ * torch.norm's backward).  k <= 64. */
 int pcadv_tnet_reg_fwd(const float* T, int B, int k, float* norms, float* reg,
                        hipStream_t stream);
 int pcadv_tnet_reg_bwd(const float* T, int B, int k, const float* grad_reg, float* dT,
                        hipStream_t stream);
 /* The regulariser of a training step in two launches (ABI 9): norms and
  * *reg as pcadv_tnet_reg_fwd, dT += pcadv_tnet_reg_bwd's gradient (the bmm's
- * dT accumulated in place), and *step_count += 1 when given (the fused
- * feature-transform cls step advances its count there, ahead of its Adam). */
+ * dT accumulated in place; a cloud with norm 0 leaves its dT untouched), and
+ * *step_count += 1 when given, once per call (the fused feature-transform cls
+ * step advances its count there on every call, ahead of its Adam). */
 int pcadv_tnet_reg_step(const float* T, int B, int k, float* norms, float* reg,
                         const float* grad_reg, float* dT, int32_t* step_count,
                         hipStream_t stream);
@@ -619,8 +621,11 @@ int pcadv_adv_step_adam(const pcadv_adv_args* args, hipStream_t stream);
  * pcadv_adv_step_workspace_bytes(B, N).  part = 3 (ABI 9): the head alone on
  * the caller's pooled features feat_gmax [B][1024] (fc1 .. the CE, and back to
  * feat_dgmax = dL/dgmax and the head's gradients), for the feature-transform
- * generator's step whose extractor runs outside; the caller advances
- * *step_count first (the dropout draws read it) and runs Adam. */
+ * generator's step whose extractor runs outside.  Part 3 does not touch
+ * *step_count: the head's dropout draws read it as it stands (the count of
+ * the completed calls), and the caller advances it afterwards (the fused
+ * feature-transform step in its pcadv_tnet_reg_step launch, on every call,
+ * with or without Adam) and runs Adam at the advanced count. */
 int pcadv_cls_step(const pcadv_adv_args* args, hipStream_t stream);
 
 #ifdef __cplusplus

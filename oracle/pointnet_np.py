@@ -565,11 +565,14 @@ def stn_backward(p, cache, dT, prefix):
 
 
 def regularizer_bwd(trans):
-    """d/dT of mean_b ||T T^T - I||_F: (2 / (B n_b)) (T T^T - I) T."""
+    """d/dT of mean_b ||T T^T - I||_F: (2 / (B n_b)) (T T^T - I) T; a cloud
+    whose norm is 0 (T T^T = I exactly) gets the zero gradient, as torch.norm's
+    backward gives there."""
     B, d, _ = trans.shape
     a = np.matmul(trans, trans.transpose(0, 2, 1)) - np.eye(d, dtype=F32)[None]
     n = np.sqrt((a.astype(np.float64) ** 2).sum((1, 2)))
-    return (np.matmul(a, trans) * (2.0 / (B * n))[:, None, None]).astype(F32)
+    scale = np.divide(2.0, B * n, out=np.zeros_like(n), where=n > 0)
+    return (np.matmul(a, trans) * scale[:, None, None]).astype(F32)
 
 
 def conv_max_at(x, w, b, am, relu_before_max=False):
