@@ -21,7 +21,9 @@
 //                 re-evaluates the winner and the runner-up as exact f32 dot
 //                 products and ranks them by those, so gmax is f32 and the argmax follows
 //                 the f32 values with the first index on ties (torch.max on
-//                 CPU).  The 128 MB conv4 output never exists.
+//                 CPU).  The 128 MB conv4 output never exists.  (fp32 mode at 64
+//                 clouds or more and N % 128 == 0 runs the same scheme on 16 waves
+//                 of 16 channels and v_mfma_f32_16x16x32_bf16: k_conv4_max<3, C4W16>.)
 #include "common.h"
 
 #include <type_traits>
@@ -1045,6 +1047,373 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
 #undef STAMP
 }
 
+// ----------------------------------------------------------------------------
+// k_conv4_max<3, C4W16>: fp32 mode's 256-channel form at N % 128 == 0, on
+// v_mfma_f32_16x16x32_bf16 with 16 waves of 16 channels.  W4's hi / lo
+// fragments are 32 VGPRs per wave (the 32-channel waves above hold 64), so the
+// kernel fits 128 VGPRs and a 1024-thread workgroup runs four waves per SIMD.
+// Measured: the adv step 0.9-1.9 us shorter than with the
+// P128 form although the launch alone is ~1 us longer (the matrix-pipe cycles
+// and the count of other vector instructions per launch are the same in both
+// forms).
+//   A = x3 (row = point lane & 15), B = W4 (col = channel lane & 15), both with
+//   k = 8 c4w_kq(lane >> 4) + j inside a 32-wide k-block; the accumulator holds
+//   channel lane & 15 at points 4 (lane >> 4) + reg of a 16-point tile, so four
+//   lanes (l, l + 16, l + 32, l + 48) share a channel.
+// Steps are 128 points (eight tiles per wave, run as four pairs whose MFMA
+// chains interleave); a pair is screened during the next pair's MFMAs with the
+// keys of the forms above, whose low bits here count rows of a 64-point span:
+// 63 - (16 (tile & 3) + reg), the lane's 4 (lane >> 4) added on decode.  A lane
+// keeps the top-2 of a span and merges it into its running top-2 once per span.
+// After the loop the four lanes of a channel merge by (value, point index) and
+// the top two are re-evaluated exactly, in the summation order of the forms
+// above (gmax is bitwise theirs).
+// LDS image: the rows of a 16-point tile sit in permuted slots (c4w_slot) and
+// the lane quarters take the 16-B chunks of a k-block in the order 0, 2, 1, 3
+// (c4w_kq): with the 272-B row stride every ds_read_b128 lane group then covers
+// the 64 banks once, and the staging map below does so for every 8-lane group
+// of its ds_write_b128.
+// ----------------------------------------------------------------------------
+#ifndef PCADV_C4_W16
+// A/B builds: 0 = that case stays with the P128 form (the diagnostic CERT / DIAG
+// builds instrument the forms above only)
+#define PCADV_C4_W16 (PCADV_C4_CERT == 0 && PCADV_C4_DIAG == 0)
+#endif
+#if PCADV_C4_W16
+struct C4W16 {};  // form tag
+constexpr int C4W_T = 1024;
+
+__device__ __forceinline__ f32x4 mfma16_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+// LDS row slot of point p of a step: rows 0-3 and 12-15 of a tile in the even
+// slots, rows 4-11 in the odd ones (the ds_read_b128 lane groups pair exactly
+// these row sets of neighbouring lane quarters)
+__device__ __forceinline__ int c4w_slot(int p) {
+  const int m = p & 15;
+  return (p & ~15) | (m < 4 ? 2 * m : (m < 12 ? 2 * m - 7 : 2 * m - 16));
+}
+// 16-B chunk of a k-block that lane quarter q multiplies (A and B alike)
+__device__ __forceinline__ int c4w_kq(int q) { return ((q & 1) << 1) | (q >> 1); }
+
+#ifndef PCADV_C4_W16_ASM
+#define PCADV_C4_W16_ASM 1  // A/B builds: 0 = the in-loop screening builds its keys in C++
+#endif
+// values [V0, V0 + CNT) of pair PP's eight (tile 2 PP + (v >> 2), reg v & 3)
+// pushed into a span's top-2 with the asm keys and one v_med3_i32 per value
+// (hipcc spends seven instructions per value on the C++ form, this is five).
+// Only for accumulators whose MFMAs retired a k-block earlier (screen_key_asm).
+template <int PP, int V0, int CNT>
+__device__ __forceinline__ void c4w_screen_asm(const f32x4 (&acc)[2], int m_ord, int m_hi, int& k1,
+                                               int& k2) {
+  if constexpr (CNT > 0) {
+    constexpr int row = 16 * ((2 * PP + (V0 >> 2)) & 3) + (V0 & 3);
+    const int key = screen_key_asm<63 - row>(acc[V0 >> 2][V0 & 3], m_ord, m_hi);
+    asm("v_med3_i32 %0, %1, %2, %0" : "+v"(k2) : "v"(key), "v"(k1));  // k2 <= k1: the new second
+    k1 = max(k1, key);
+    c4w_screen_asm<PP, V0 + 1, CNT - 1>(acc, m_ord, m_hi, k1, k2);
+  }
+}
+
+template <int NP4, typename Form>
+__global__ void __launch_bounds__(C4W_T)
+k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict__ w4,
+            const float* __restrict__ b4, float* __restrict__ gmax, int32_t* __restrict__ gidx,
+            uint64_t* __restrict__ stamps, int relu) {
+  static_assert(NP4 == 3 && std::is_same<Form, C4W16>::value, "fp32 mode's 16-channel-wave form");
+  (void)stamps;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  C4Lds& L = *reinterpret_cast<C4Lds*>(smem);
+  int bid = blockIdx.x;  // XCD-aware order, as above
+  const int nwg = gridDim.x;
+  if ((nwg & 7) == 0) bid = (bid & 7) * (nwg >> 3) + (bid >> 3);
+  const int c = bid >> 2, cb = bid & 3;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, qt = lane >> 4;
+  const float* xc = x3g + (size_t)c * N * 128;
+  const int S = N >> 7;
+  constexpr int P = 128;
+
+  // staging map: tid bits 0, 1, 3 = the row eighth (16 consecutive k), bit 2 =
+  // row bit 2, bits 4, 5 = row bits 0, 1, bits 6.. = row bits 3..: a wave loads
+  // 8 whole rows (4 KB contiguous), and 8 consecutive lanes write four chunks
+  // of a row in an even slot and four of a row in an odd slot
+  const int srow = ((tid >> 4) & 3) | (tid & 4) | ((tid >> 6) << 3);
+  const int sk = 16 * ((tid & 3) | ((tid >> 1) & 4));
+  const int soff = c4w_slot(srow) * C4_SB + sk;
+  f32x4 stg[4];
+  auto stage_load = [&](int s) {  // past the cloud it re-reads the last row (never screened)
+    const int p = min(s * P + srow, N - 1);
+    const f32x4* src = reinterpret_cast<const f32x4*>(xc + (size_t)p * 128 + sk);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) stg[j] = src[j];
+  };
+  bf16x8 shi[2], slo[2];  // the staged row piece split to bf16 hi / lo
+  auto stage_split = [&](int j0, int j1) {
+#pragma unroll
+    for (int j = j0; j < j1; ++j) {
+      const float v = stg[j >> 2][j & 3];
+      const __bf16 hb = (__bf16)v;
+      shi[j >> 3][j & 7] = hb;
+      slo[j >> 3][j & 7] = (__bf16)(v - (float)hb);
+    }
+  };
+  auto stage_store = [&](int buf) {
+    bf16x8* dh = reinterpret_cast<bf16x8*>(&L.x[buf][0][soff]);
+    bf16x8* dl = reinterpret_cast<bf16x8*>(&L.x[buf][1][soff]);
+    dh[0] = shi[0];
+    dh[1] = shi[1];
+    dl[0] = slo[0];
+    dl[1] = slo[1];
+  };
+  stage_load(0);
+  // W4 rows of this wave's 16 channels: coalesced loads into the wave's own LDS
+  // rows, then each lane takes its quarter's 8 k of every k-block, split to hi / lo
+  const int kq8 = 8 * c4w_kq(qt);
+  bf16x8 bh[4], bl[4];
+  {
+    const float* wsrc = w4 + (size_t)(cb * C4_CB + 16 * wave) * 128;
+    float* wl = reinterpret_cast<float*>(smem) + wave * 16 * C4_WS;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int e = 4 * (lane + 64 * i);  // float index in the 16 x 128 block
+      *reinterpret_cast<f32x4*>(wl + (e >> 7) * C4_WS + (e & 127)) =
+          *reinterpret_cast<const f32x4*>(wsrc + e);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const float* wrow = wl + l15 * C4_WS + kq8;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+      const f32x4 u0 = *reinterpret_cast<const f32x4*>(wrow + 32 * kb);
+      const f32x4 u1 = *reinterpret_cast<const f32x4*>(wrow + 32 * kb + 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = j < 4 ? u0[j] : u1[j - 4];
+        const __bf16 hb = (__bf16)v;
+        bh[kb][j] = hb;
+        bl[kb][j] = (__bf16)(v - (float)hb);
+      }
+    }
+  }
+  __syncthreads();  // every wave holds its fragments before tile 0 overwrites the staging rows
+  stage_split(0, 16);
+  stage_store(0);
+  stage_load(1);
+  __syncthreads();
+
+  // running top-2 keys of this lane (r1 >= r2) with their 64-point spans, and
+  // the top-2 of the span being screened
+  int r1 = KEY_NONE, r2 = KEY_NONE, t1 = -1, t2 = -1;
+  int k1 = KEY_NONE, k2 = KEY_NONE;
+  f32x4 acc[2][2];  // [pair parity][tile of the pair]
+  const int xoff = c4w_slot(l15) * C4_SB + kq8;
+  // values [V0, V0 + CNT) of pair PP's eight (tile PP * 2 + (v >> 2), reg v & 3)
+  auto screen = [&](auto PP, int v0, int cnt) {
+    constexpr int pp = decltype(PP)::value;
+#pragma unroll
+    for (int v = v0; v < v0 + cnt; ++v) {
+      const int row = 16 * ((2 * pp + (v >> 2)) & 3) + (v & 3);
+      const int key = screen_key(acc[pp & 1][v >> 2][v & 3], 63 - row);
+      k2 = max(min(key, k1), k2);  // median(key, k1, k2) for k2 <= k1: v_med3_i32
+      k1 = max(k1, key);
+    }
+  };
+  const int m_ord = 0x7fffffc0, m_hi = ~63;
+  auto span_done = [&](int u) {
+    pair_merge<true>(k1, u, k2, u, r1, t1, r2, t2);
+    k1 = KEY_NONE;
+    k2 = KEY_NONE;
+  };
+  // One pair of tiles (2 pp, 2 pp + 1 of step s): 24 MFMAs in four k-blocks,
+  // each k-block's region also holding two screened values of the previous
+  // pair and this region's share of the staging work
+  auto pair = [&](int s, auto PP, auto SCREEN) {
+    constexpr int pp = decltype(PP)::value, cs = pp & 1;
+    using PREV = std::integral_constant<int, (pp + 3) & 3>;
+    const int buf = s & 1;
+    const __bf16* xh = &L.x[buf][0][32 * pp * C4_SB + xoff];
+    const __bf16* xl = &L.x[buf][1][32 * pp * C4_SB + xoff];
+    bf16x8 fa[2][2][2];  // A fragments, a 2-deep ring: [k-block % 2][tile][hi, lo]
+    auto frag = [&](int kb) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        fa[kb & 1][j][0] = *reinterpret_cast<const bf16x8*>(xh + 16 * j * C4_SB + 32 * kb);
+        fa[kb & 1][j][1] = *reinterpret_cast<const bf16x8*>(xl + 16 * j * C4_SB + 32 * kb);
+      }
+    };
+    frag(0);
+    acc[cs][0] = f32x4{};
+    acc[cs][1] = f32x4{};
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (kb + 1 < 4) {  // issued first: a whole k-block (six MFMAs) ahead of its use
+        frag(kb + 1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const bf16x8 ah0 = fa[kb & 1][0][0], al0 = fa[kb & 1][0][1];
+      const bf16x8 ah1 = fa[kb & 1][1][0], al1 = fa[kb & 1][1][1];
+      acc[cs][0] = mfma16_bf16(al0, bh[kb], acc[cs][0]);
+      acc[cs][1] = mfma16_bf16(al1, bh[kb], acc[cs][1]);
+      acc[cs][0] = mfma16_bf16(ah0, bl[kb], acc[cs][0]);
+      acc[cs][1] = mfma16_bf16(ah1, bl[kb], acc[cs][1]);
+      acc[cs][0] = mfma16_bf16(ah0, bh[kb], acc[cs][0]);
+      acc[cs][1] = mfma16_bf16(ah1, bh[kb], acc[cs][1]);
+      if constexpr (decltype(SCREEN)::value) {
+        if constexpr (PCADV_C4_W16_ASM) {
+          // 3 + 3 + 2 values over k-blocks 1..3; none in k-block 0, so the
+          // previous pair's MFMAs have retired before the asm reads them
+          // (tools/check_asm_hazards.py checks the distance in the ISA)
+          if (kb == 1) c4w_screen_asm<PREV::value, 0, 3>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
+          if (kb == 2) c4w_screen_asm<PREV::value, 3, 3>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
+          if (kb == 3) c4w_screen_asm<PREV::value, 6, 2>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
+        } else {
+          screen(PREV{}, 2 * kb, 2);
+        }
+        // pin the keys to this region (otherwise the IR passes sink the whole
+        // screening below the MFMAs, next to its only use)
+        asm volatile("" ::"v"(k1), "v"(k2));
+      }
+      if constexpr (pp < 2) {  // split the staged f32 row piece, 2 values per k-block
+        stage_split(8 * pp + 2 * kb, 8 * pp + 2 * kb + 2);
+        asm volatile("" ::"v"(shi[pp]), "v"(slo[pp]));
+      }
+      if (pp == 2 && kb == 0) {
+        stage_store(buf ^ 1);  // the next step's tile (buffer free since the barrier)
+        stage_load(s + 2);     // into the staging registers just freed
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (decltype(SCREEN)::value && (PREV::value & 1))
+      span_done((4 * s + pp - 1) >> 1);
+  };
+  using T_ = std::true_type;
+  using F_ = std::false_type;
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>;
+  using I3 = std::integral_constant<int, 3>;
+  pair(0, I0{}, F_{});
+  pair(0, I1{}, T_{});
+  pair(0, I2{}, T_{});
+  pair(0, I3{}, T_{});
+  __syncthreads();
+  for (int s = 1; s < S; ++s) {
+    pair(s, I0{}, T_{});
+    pair(s, I1{}, T_{});
+    pair(s, I2{}, T_{});
+    pair(s, I3{}, T_{});
+    __syncthreads();
+  }
+  // The lane's ids again, from a thread id the compiler cannot trace: what the
+  // tail derives from them would otherwise be computed before the loop and
+  // held (or spilled) through it
+  int etid = threadIdx.x;
+  asm volatile("" : "+v"(etid));
+  const int elane = etid & 63, ewave = etid >> 6, el15 = etid & 15, eqt = elane >> 4;
+  const int eo = cb * C4_CB + 16 * ewave + el15;
+  // W4 rows of the exact re-evaluation (eight lanes per row, see above),
+  // fetched while the last pair is screened and merged
+  const int oc = elane >> 3, part = elane & 7;
+  const float* wbase = w4 + (size_t)(cb * C4_CB + 16 * ewave) * 128 + 16 * part;
+  f32x4 wv[2][4];
+#pragma unroll
+  for (int G = 0; G < 2; ++G)
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      wv[G][u] = *reinterpret_cast<const f32x4*>(wbase + (size_t)(8 * G + oc) * 128 + 4 * u);
+  screen(I3{}, 0, 8);
+  span_done(2 * S - 1);
+
+  // decode this lane's pair (rows carry the lane quarter's offset), ordered by
+  // (value, global index)
+  const int hm = 4 * eqt;
+  auto key_row64 = [](int k) { return 63 - (k & 63); };
+  int a1 = t1 < 0 ? 0x7fffffff : t1 * 64 + key_row64(r1) + hm;
+  int a2 = t2 < 0 ? 0x7fffffff : t2 * 64 + key_row64(r2) + hm;
+  float v1 = t1 < 0 ? -INFINITY : key_value(r1), v2 = t2 < 0 ? -INFINITY : key_value(r2);
+  if (ranks_before(v2, a2, v1, a1)) {  // equal truncated values: order by index
+    const float tv = v1;
+    v1 = v2;
+    v2 = tv;
+    const int ta = a1;
+    a1 = a2;
+    a2 = ta;
+  }
+  // the four lanes of a channel: two butterfly steps, each inserting the other
+  // side's pair, leave the channel's top-2 in all four
+#pragma unroll
+  for (int xm = 16; xm <= 32; xm <<= 1) {
+    const float w1v = __shfl_xor(v1, xm), w2v = __shfl_xor(v2, xm);
+    const int j1 = __shfl_xor(a1, xm), j2 = __shfl_xor(a2, xm);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const float v = q == 0 ? w1v : w2v;
+      const int p = q == 0 ? j1 : j2;
+      const bool a = ranks_before(v, p, v1, a1);
+      const bool b = !a && ranks_before(v, p, v2, a2);
+      const float nv2 = a ? v1 : (b ? v : v2);
+      const int na2 = a ? a1 : (b ? p : a2);
+      v1 = a ? v : v1;
+      a1 = a ? p : a1;
+      v2 = nv2;
+      a2 = na2;
+    }
+  }
+  if (a1 == 0x7fffffff) a1 = 0;
+  const bool near = a2 != 0x7fffffff;
+  const int b2 = near ? a2 : a1;
+  // Exact dot products of the top two, eight lanes per row as above: in pass G
+  // lane l takes channel 8 G + (l >> 3) and terms 16 (l & 7) .. + 16
+  f32x4 av[2][4], bv[2][4];
+#pragma unroll
+  for (int G = 0; G < 2; ++G) {
+    const int ch = 8 * G + oc;
+    const int p1 = __shfl(a1, ch), p2 = __shfl(b2, ch);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      av[G][u] = *reinterpret_cast<const f32x4*>(xc + (size_t)p1 * 128 + 16 * part + 4 * u);
+      bv[G][u] = *reinterpret_cast<const f32x4*>(xc + (size_t)p2 * 128 + 16 * part + 4 * u);
+    }
+  }
+  float res1 = 0.f, res2 = 0.f;
+#pragma unroll
+  for (int G = 0; G < 2; ++G) {
+    float e1 = 0.f, e2 = 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        e1 = fmaf(av[G][u][t], wv[G][u][t], e1);
+        e2 = fmaf(bv[G][u][t], wv[G][u][t], e2);
+      }
+    e1 = octet_sum(e1);
+    e2 = octet_sum(e2);
+    // channel 8 G + k was summed in lanes 8 k .. 8 k + 7: owner lanes l15 in
+    // [8 G, 8 G + 8) (every quarter) fetch it
+    const int src = 8 * (el15 & 7);
+    const float f1 = __shfl(e1, src), f2 = __shfl(e2, src);
+    if ((el15 >> 3) == G) {
+      res1 = f1;
+      res2 = f2;
+    }
+  }
+  const float bias = b4[eo];
+  const float e1 = res1 + bias, e2 = res2 + bias;
+  const bool second = near && ranks_before(e2, a2, e1, a1);
+  if (eqt == 0) {
+    float gv = second ? e2 : e1;
+    int gi = second ? a2 : a1;
+    if (relu && gv <= 0.f) gv = 0.f, gi = 0;  // all-non-positive rows: see above
+    gmax[(size_t)c * C4_O + eo] = gv;
+    gidx[(size_t)c * C4_O + eo] = gi;
+  }
+}
+
+#endif  // PCADV_C4_W16
+
 #if PCADV_C4_CERT
 // diagnostic builds only: read (and reset) the certification counters
 int c4_cert_read(unsigned* host) {
@@ -1064,6 +1433,16 @@ template <int NP3, int NP4>
 static int feat_fwd_attrs() {
   static bool attr_set = false;
   if (!attr_set) {
+#if PCADV_C4_W16
+    if constexpr (NP4 == 3) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, C4W16>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)sizeof(C4Lds)) != hipSuccess) {
+        set_error("feat_fwd: cannot reserve LDS (%zu bytes)", sizeof(C4Lds));
+        return PCADV_EHIP;
+      }
+    }
+#endif
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sizeof(C4Lds)) != hipSuccess ||
@@ -1119,10 +1498,18 @@ static int launch_conv4_max_np(const float* x3, int C, int N, const float* w4, c
     hipLaunchKernelGGL((k_conv4_max<NP4, true, XB>), dim3(C * (2 * C4_O / C4_CB)),
                        dim3(c4_threads<NP4, true, XB>()),
                        sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
-  else if (PCADV_C4_P128 && N % 128 == 0 && !stamps)
+  else if (PCADV_C4_P128 && N % 128 == 0 && !stamps) {
+#if PCADV_C4_W16  // fp32 mode: 16-channel waves on 16x16x32 MFMAs, four waves per SIMD
+    if constexpr (NP4 == 3 && !XB) {
+      hipLaunchKernelGGL((k_conv4_max<NP4, C4W16>), dim3(C * (C4_O / C4_CB)), dim3(C4W_T),
+                         sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
+      PC_HIP_CHECK_LAUNCH("k_conv4_max");
+      return PCADV_OK;
+    }
+#endif
     hipLaunchKernelGGL((k_conv4_max<NP4, false, XB, true>), dim3(C * (C4_O / C4_CB)), dim3(C4_T),
                        sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
-  else
+  } else
     hipLaunchKernelGGL((k_conv4_max<NP4, false, XB>), dim3(C * (C4_O / C4_CB)), dim3(C4_T),
                        sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
   PC_HIP_CHECK_LAUNCH("k_conv4_max");

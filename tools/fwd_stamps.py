@@ -1,6 +1,8 @@
 """Per-phase timestamps of the fused feature forward / backward (diagnostic
 build: `make stamps` -> build/stamps/libpcadv_stamps.so, never the product
-library).  s_memrealtime ticks at 100 MHz (10 ns).
+library).  s_memrealtime ticks at 100 MHz (10 ns).  A launch with stamps runs
+k_conv4_max's plain 64-point form whatever the shape (not the two-group, P128
+or 16-channel-wave forms): the stamp layout below is that form's.
 
     python tools/fwd_stamps.py [C] [N]
 """
