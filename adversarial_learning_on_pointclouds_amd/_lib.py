@@ -188,6 +188,9 @@ SIGNATURES = {
     "pcadv_iter_epilogue": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "pcadv_row_ce_workspace_bytes": (_sz, [_i]),
     "pcadv_row_ce": (_i, [_vp, _i64, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "pcadv_row_eval_workspace_bytes": (_sz, [_i]),
+    "pcadv_row_eval": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp,
+                            _vp, _vp, _sz, _vp]),
     "pcadv_adv_step_workspace_bytes": (_sz, [_i, _i]),
     "pcadv_adv_step": (_i, [ctypes.POINTER(AdvArgs), _vp]),
     "pcadv_adv_step_adam": (_i, [ctypes.POINTER(AdvArgs), _vp]),

@@ -12,6 +12,19 @@ seg_classes = {'Airplane': [0, 1, 2, 3], 'Bag': [4, 5], 'Cap': [6, 7], 'Car': [8
                'Rocket': [41, 42, 43], 'Skateboard': [44, 45, 46], 'Table': [47, 48, 49]}
 
 
+def part_ranges():
+    """[(first part label, part count)] per category in object_names order:
+    seg_classes as the table the device metric reads (pcadv_row_eval), which
+    takes each category's parts as one contiguous label range."""
+    table = []
+    for name in object_names:
+        parts = seg_classes[name]
+        assert parts == list(range(parts[0], parts[0] + len(parts))), \
+            f"seg_classes[{name!r}] is not a contiguous label range"
+        table.append((parts[0], len(parts)))
+    return table
+
+
 def get_iou(gt, pred, cls_gt):
     """utils/metric.py:19-30: mean over the category's parts of |gt & pred| /
     |gt | pred|, a part absent from both counting 1."""

@@ -30,11 +30,19 @@ from .utils import make_D_label
 
 def run_testing(dataloader, model, criterion, logger, test_iter, writer, args):
     """utils/trainer.py:30-69 (accuracy normalised by batch_size * len(loader),
-    as the reference does)."""
+    as the reference does).  A ModelNet DeviceCloudLoader with a plain
+    PointNetCls and CrossEntropyLoss takes the native pass (evaluate.ClsEvaluator:
+    a graph replay per full batch, the metrics summed on the device, one copy
+    per pass) unless args.native_eval is false; every other configuration runs
+    the reference's body below."""
     model.eval()
     total_accuracy = 0.0
     total_loss = 0.0
-    for batch_idx, data in enumerate(dataloader):
+    ev = _native_evaluator(dataloader, model, criterion, args, seg=False)
+    if ev is not None:
+        r = ev.run(use_graph=bool(getattr(args, "use_graph", True)))
+        total_accuracy, total_loss = r["correct"], r["loss_sum"]
+    for batch_idx, data in enumerate(dataloader if ev is None else ()):
         pts, cls = data
         pts, cls = pts.float().to(args.device), cls.long().to(args.device)
         with torch.set_grad_enabled(False):
@@ -50,6 +58,42 @@ def run_testing(dataloader, model, criterion, logger, test_iter, writer, args):
         writer.add_scalar("Loss/test_cls", total_loss / denom, test_iter)
         writer.add_scalar("Accuracy/test", total_accuracy / denom, test_iter)
     return total_accuracy / denom, total_loss / denom
+
+
+def _native_evaluator(dataloader, model, criterion, args, seg):
+    """The cached evaluate.ClsEvaluator / SegEvaluator of `model` when the test
+    pass is one the native path covers, else None (the module path runs): a
+    DeviceCloudLoader itself (not a wrapper yielding from one) of the task's
+    kind, one process, at most MAX_FUSED_B clouds per batch; PointNetCls
+    without the feature transform / PointNetSeg, at most 64 classes; a plain
+    CrossEntropyLoss (mean, unweighted, unsmoothed, ignore_index outside the
+    labels); args.native_eval not false."""
+    from . import evaluate
+    from .dataset import DeviceCloudLoader
+    from .seg import PointNetSeg
+    if not getattr(args, "native_eval", True) or type(dataloader) is not DeviceCloudLoader:
+        return None
+    if (dataloader.kind != ("shapenet_gt" if seg else "modelnet_gt") or dataloader.world != 1
+            or dataloader.B > MAX_FUSED_B or str(args.device).split(":")[0] != "cuda"):
+        return None
+    if seg:
+        if not isinstance(model, PointNetSeg):
+            return None
+        ncls = model.output_dim
+    else:
+        if not isinstance(model, PointNetCls) or model.feature_transform:
+            return None
+        ncls = model.fc3.out_features
+    if not 2 <= ncls <= evaluate.MAX_CLASSES:
+        return None
+    if (type(criterion) is not torch.nn.CrossEntropyLoss or criterion.weight is not None
+            or criterion.reduction != "mean" or criterion.label_smoothing != 0.0
+            or 0 <= criterion.ignore_index < ncls):
+        return None
+    if any(p.device != dataloader.device for p in model.parameters()):
+        return None
+    return evaluate.evaluator_for(model, dataloader,
+                                  evaluate.SegEvaluator if seg else evaluate.ClsEvaluator)
 
 
 # the fused native steps take at most this many clouds per batch (capi.hip:
@@ -1023,12 +1067,21 @@ def run_training_pointnet_cls(trainloader_gt, trainloader_gt_iter, testloader, m
 def run_testing_seg(dataloader, dataset, model, criterion, logger, test_iter, writer, args):
     """utils/trainer.py:72-143: point accuracy, loss and the category / all-shape
     mean part IoU (the reference's np.object container, removed from numpy,
-    becomes a list of lists)."""
+    becomes a list of lists).  A ShapeNet DeviceCloudLoader with PointNetSeg
+    and a plain CrossEntropyLoss takes the native pass (evaluate.SegEvaluator:
+    per-cloud IoU records from the device, the means over them formed here as
+    below) unless args.native_eval is false."""
     model.eval()
     total_accuracy = 0.0
     total_loss = 0.0
     shape_ious = [[] for _ in object_names]
-    for batch_idx, data in enumerate(dataloader):
+    ev = _native_evaluator(dataloader, model, criterion, args, seg=True)
+    if ev is not None:
+        r = ev.run(use_graph=bool(getattr(args, "use_graph", True)))
+        total_accuracy, total_loss = r["correct"] / float(args.input_pts), r["loss_sum"]
+        for iou, c in zip(r["iou"].tolist(), r["cat"].tolist()):
+            shape_ious[c].append(iou)
+    for batch_idx, data in enumerate(dataloader if ev is None else ()):
         pts, cls, seg = data
         pts, cls, seg = pts.float().to(args.device), cls.to(args.device), seg.long().to(args.device)
         with torch.set_grad_enabled(False):

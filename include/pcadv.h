@@ -483,6 +483,35 @@ int pcadv_row_ce(const float* logits, int64_t ld, const int64_t* labels, int M, 
                  float scale, float* loss, float* dlogits, void* workspace,
                  size_t workspace_bytes, hipStream_t stream);
 
+/* Evaluation metrics of one batch on the device (the trainers' test passes,
+ * evaluate.py): for logits [M][ncls] (row stride ld >= ncls, 2 <= ncls <= 64)
+ * and labels int64 [M] (each in [0, ncls)), per row the argmax (the FIRST index
+ * on exact ties, as np.argmax / torch.max on the host) into pred (optional)
+ * and the row's cross entropy; per call, into the caller-owned device
+ * accumulator acc[4] (zeroed by the caller before a pass):
+ *   acc[0] += number of rows with pred == label,
+ *   acc[1] += the f32 mean of the M rows' cross entropy (what loss.item() gives),
+ *   acc[2] += M,   acc[3] += 1.
+ * The mean is a fixed-order sum (no floating-point atomics): two runs on the
+ * same inputs leave the same bits.
+ * rows_per_group = N > 0 (M % N == 0) adds the mean part IoU of each group
+ * (cloud) g of N rows (utils/metric.py:19-30): its category is
+ * group_cat[g * cat_stride], whose parts are the labels [cat_parts[2c],
+ * cat_parts[2c] + cat_parts[2c + 1]) (device table [ncat][2], at most 8 parts);
+ * a part in neither the labels nor the predictions counts 1, the others
+ * |gt & pred| / |gt | pred| in f64, summed in part order and divided by the
+ * part count: bitwise the host's np.mean.  The IoU goes to iou_out[base + g]
+ * and the category to cat_out[base + g], base = *cursor * (M / N) (cursor: a
+ * device int32, NULL for 0), so a replayed graph writes each batch's records
+ * at its own place.  A category outside [0, ncat) gives a NaN record.
+ * Calls sharing acc or the workspace must be ordered on one stream. */
+size_t pcadv_row_eval_workspace_bytes(int M);
+int pcadv_row_eval(const float* logits, int64_t ld, const int64_t* labels, int M, int ncls,
+                   int32_t* pred, int rows_per_group, const int64_t* group_cat,
+                   int64_t cat_stride, const int32_t* cat_parts, int ncat,
+                   const int32_t* cursor, double* iou_out, int32_t* cat_out, double* acc,
+                   void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* ---- Adam (torch.optim.Adam semantics, amsgrad=False, weight_decay=0) ------
  * step_count: device int32, incremented by this call (t = *step_count + 1). */
 int pcadv_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
