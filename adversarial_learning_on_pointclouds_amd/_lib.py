@@ -123,6 +123,25 @@ class GatherJob(ctypes.Structure):
     ]
 
 
+class PwdiscArgs(ctypes.Structure):
+    """Mirror of pcadv_pwdisc_args (include/pcadv.h)."""
+
+    _fields_ = [
+        ("logits", _vp), ("ld", _i64),
+        ("ncls", _i), ("n0", _i), ("n1", _i), ("t0", _i), ("t1", _i),
+        ("w", _vp * 4), ("b", _vp * 4),
+        ("out", _vp), ("argc", _vp), ("losses", _vp),
+        ("soft0", _vp), ("soft1", _vp), ("soft_out", _vp),
+        ("rng_seed", _u64), ("step_count", _vp),
+        ("dout_d", _vp), ("dout_adv", _vp), ("lambda_adv", _f),
+        ("dw", _vp * 4), ("db", _vp * 4),
+        ("dlogits", _vp), ("ldd", _i64), ("max_workgroups", _i),
+        ("workspace", _vp), ("workspace_bytes", _sz), ("x_out", _vp),
+    ]
+
+
+PWD_NONE, PWD_SOFTMAX, PWD_LOG_SOFTMAX = 0, 1, 2
+
 # name -> (restype, argtypes); every symbol of include/pcadv.h
 SIGNATURES = {
     "pcadv_last_error": (ctypes.c_char_p, []),
@@ -195,6 +214,9 @@ SIGNATURES = {
     "pcadv_adv_step": (_i, [ctypes.POINTER(AdvArgs), _vp]),
     "pcadv_adv_step_adam": (_i, [ctypes.POINTER(AdvArgs), _vp]),
     "pcadv_cls_step": (_i, [ctypes.POINTER(AdvArgs), _vp]),
+    "pcadv_pwdisc_workspace_bytes": (_sz, [_i64, _i]),
+    "pcadv_pwdisc_forward": (_i, [ctypes.POINTER(PwdiscArgs), _vp]),
+    "pcadv_pwdisc_backward": (_i, [ctypes.POINTER(PwdiscArgs), _vp]),
 }
 
 _lib = None

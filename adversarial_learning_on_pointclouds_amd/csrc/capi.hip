@@ -122,6 +122,9 @@ int launch_gather_clouds(const float*, int64_t, int, int, const int64_t*, int, c
 int launch_iter_epilogue(int32_t*, int, const float*, int, float*, int, int32_t*, hipStream_t);
 int check_iter_epi(const IterEpi&);
 int launch_gather_multi(const pcadv_gather_job*, int, hipStream_t);
+size_t pwdisc_workspace_bytes(long long, int);
+int launch_pwdisc_fwd(const pcadv_pwdisc_args*, hipStream_t);
+int launch_pwdisc_bwd(const pcadv_pwdisc_args*, hipStream_t);
 size_t row_ce_workspace_bytes(int);
 int launch_row_ce(const float*, long long, const int64_t*, int, int, float, float*, float*, void*,
                   size_t, hipStream_t);
@@ -899,5 +902,17 @@ int pcadv_adv_step_adam(const pcadv_adv_args* args, hipStream_t stream) {
 }
 
 int pcadv_cls_step(const pcadv_adv_args* args, hipStream_t stream) { return cls_step(args, stream); }
+
+size_t pcadv_pwdisc_workspace_bytes(int64_t rows, int max_workgroups) {
+  return pwdisc_workspace_bytes(rows, max_workgroups);
+}
+
+int pcadv_pwdisc_forward(const pcadv_pwdisc_args* args, hipStream_t stream) {
+  return launch_pwdisc_fwd(args, stream);
+}
+
+int pcadv_pwdisc_backward(const pcadv_pwdisc_args* args, hipStream_t stream) {
+  return launch_pwdisc_bwd(args, stream);
+}
 
 }  // extern "C"

@@ -1,0 +1,652 @@
+// PointwiseDiscNet (models/discriminator.py:53-79) fused for the adversarial
+// segmentation step (utils/trainer.py:849-1026): per point a softmax /
+// log_softmax of the generator's logits, conv1..conv4 + ReLU (ncls -> 64 -> 64
+// -> 64 -> 128) on the exact f32 MFMA, the max over the 128 channels and the
+// three BCE-with-logits terms of the iteration; the backward recomputes x1..x3
+// and forms every weight gradient and the no-GT rows' input gradient.
+//
+// Tiles of 64 points, persistent workgroups of 4 waves.  Every MFMA runs in k
+// order (mfma_rows_x_wt), and the backward calls the same device functions as
+// the forward, so its recomputed activations (and ReLU masks) are the forward's
+// bits.  No floating-point atomics: the loss terms and the weight-gradient
+// slabs are summed in a fixed order.
+#include <cmath>
+
+#include "common.h"
+
+namespace pcadv {
+
+namespace {
+
+constexpr int PD_T = 256;     // threads per workgroup
+constexpr int PD_ROWS = 64;   // points per tile
+constexpr int PD_S = S64;     // LDS row stride of the 64-wide buffers
+constexpr int PD_S4 = S128;   // ... of conv4's 128-wide output
+constexpr int PD_FWD_WG = 512;  // default persistent grids: 2 (forward) and 1
+constexpr int PD_BWD_WG = 256;  // (backward) workgroups per CU (LDS bound)
+
+// one workgroup's weight-gradient slab (floats): dW1 padded to K = 64
+constexpr int SL_W1 = 0, SL_W2 = 4096, SL_W3 = 8192, SL_W4 = 12288;
+constexpr int SL_B1 = 20480, SL_B2 = 20544, SL_B3 = 20608, SL_B4 = 20672;
+constexpr int SL_N = 20800;
+constexpr size_t WS_HEAD = 256;  // the ticket, alone on its line
+
+struct PwdNet {
+  const float* logits;
+  long long ld;
+  int ncls, n0, n1, t0, t1;
+  const float* w[4];
+  const float* b[4];
+};
+
+struct PwdFwdOut {
+  float* out;
+  int32_t* argc;
+  float* losses;        // [4] or NULL: no loss terms
+  const float* soft0;   // explicit labels (parity mode) or NULL: drawn here
+  const float* soft1;
+  float* soft_out;      // optional: the labels used
+  uint64_t seed;
+  const int32_t* step;
+  float* dout_d;
+  float* dout_adv;
+  unsigned* ticket;
+  float* partial;       // [ntiles][3]
+};
+
+struct PwdBwdArgs {
+  const float* out;
+  const int32_t* argc;
+  const float* dout_d;
+  const float* dout_adv;  // NULL: no input gradient
+  float lambda_adv;
+  float* dlogits;
+  long long ldd;
+  float* slabs;
+  float* x_out;  // optional [3][M][64]: the recomputed x1..x3 (tests)
+};
+
+// The transformed input tile x0 [64][64] (columns >= ncls and rows >= M zero):
+// four lanes per row, column c = q + 4 i.  The row max and the exp sum combine
+// the four lanes' partials by xor shuffles (commutative: every lane holds the
+// same bits), in one fixed order.
+__device__ __forceinline__ void pwd_load_x0(const PwdNet& p, int r0, int tid, float* x0) {
+  const int row = tid >> 2, q = tid & 3;
+  const long long g = (long long)r0 + row;
+  const bool in = g < (long long)p.n0 + p.n1;
+  const int tr = g < p.n0 ? p.t0 : p.t1;
+  const float* src = p.logits + (size_t)(in ? g : 0) * p.ld;
+  float v[16];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = q + 4 * i;
+    const bool ok = in && c < p.ncls;
+    v[i] = ok ? src[c] : -INFINITY;
+    mx = fmaxf(mx, v[i]);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 1));
+  mx = fmaxf(mx, __shfl_xor(mx, 2));
+  if (!in) mx = 0.f;
+  float e[16];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    e[i] = (in && q + 4 * i < p.ncls) ? expf(v[i] - mx) : 0.f;
+    s += e[i];
+  }
+  s += __shfl_xor(s, 1);
+  s += __shfl_xor(s, 2);
+  const float lg = logf(s);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = q + 4 * i;
+    float y = v[i];
+    if (tr == PCADV_PWD_SOFTMAX) y = e[i] / s;
+    if (tr == PCADV_PWD_LOG_SOFTMAX) y = (v[i] - mx) - lg;
+    x0[row * PD_S + c] = (in && c < p.ncls) ? y : 0.f;
+  }
+}
+
+// B fragments of W [O][ldw] for output columns [oc, oc + 32), k < kmax (zero
+// past it: conv1's ncls columns padded to the MFMA's K = 64)
+template <bool PAD>
+__device__ __forceinline__ void pwd_frags(const float* __restrict__ w, int ldw, int kmax, int oc,
+                                          int lane, f32x4 (&bf)[8]) {
+  const int r = lane & 31, h = lane >> 5;
+  const float* row = w + (size_t)(oc + r) * ldw;
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    if constexpr (PAD) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = 8 * g + 4 * h + j;
+        bf[g][j] = k < kmax ? row[k] : 0.f;
+      }
+    } else {
+      bf[g] = *reinterpret_cast<const f32x4*>(row + 8 * g + 4 * h);
+    }
+  }
+}
+
+// B fragments of the transposed product dz W (W [64][ldw]): output columns
+// [oc, oc + 32) of W's columns (zero from ncols on), k over W's 64 rows
+__device__ __forceinline__ void pwd_frags_t(const float* __restrict__ w, int ldw, int ncols, int oc,
+                                            int lane, f32x4 (&bf)[8]) {
+  const int r = lane & 31, h = lane >> 5;
+  const bool ok = oc + r < ncols;
+  const float* col = w + (ok ? oc + r : 0);
+#pragma unroll
+  for (int g = 0; g < 8; ++g)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bf[g][j] = ok ? col[(size_t)(8 * g + 4 * h + j) * ldw] : 0.f;
+}
+
+// one 64 -> 64 layer + ReLU of the tile: wave = (row tile wave >> 1, column
+// tile wave & 1)
+__device__ __forceinline__ void pwd_layer64(const float* in, float* out, const f32x4 (&bf)[8],
+                                            float bias, int wave, int lane) {
+  const int r = lane & 31, oc = 32 * (wave & 1), rt = wave >> 1;
+  f32x16 acc = {};
+  acc = mfma_rows_x_wt<64>(in + 32 * rt * PD_S, PD_S, bf, acc, lane);
+#pragma unroll
+  for (int e = 0; e < 16; ++e)
+    out[(32 * rt + acc_row(e, lane)) * PD_S + oc + r] = act_fwd(acc[e] + bias, ACT_RELU);
+}
+
+// x0 -> x1 -> x2 -> x3 (each [64][PD_S]); the caller has synchronised after
+// writing x0.  Ends with a barrier: x3 is readable by every wave.
+__device__ __forceinline__ void pwd_chain3(const PwdNet& p, float* x0, float* x1, float* x2,
+                                           float* x3, int wave, int lane) {
+  const int r = lane & 31, oc = 32 * (wave & 1);
+  f32x4 bf[8];
+  pwd_frags<true>(p.w[0], p.ncls, p.ncls, oc, lane, bf);
+  pwd_layer64(x0, x1, bf, p.b[0][oc + r], wave, lane);
+  pwd_frags<false>(p.w[1], 64, 64, oc, lane, bf);
+  __syncthreads();
+  pwd_layer64(x1, x2, bf, p.b[1][oc + r], wave, lane);
+  pwd_frags<false>(p.w[2], 64, 64, oc, lane, bf);
+  __syncthreads();
+  pwd_layer64(x2, x3, bf, p.b[2][oc + r], wave, lane);
+  __syncthreads();
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+struct PwdFwdLds {
+  alignas(16) float xa[PD_ROWS * PD_S];
+  alignas(16) float xb[PD_ROWS * PD_S];
+  alignas(16) float y4[PD_ROWS * PD_S4];
+  float lt[3][PD_ROWS];
+  int last;
+};
+
+__global__ void __launch_bounds__(PD_T, 2) k_pwd_fwd(PwdNet p, PwdFwdOut o, int ntiles) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  PwdFwdLds& L = *reinterpret_cast<PwdFwdLds*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31;
+  const long long M = (long long)p.n0 + p.n1;
+  uint32_t stepv = 0;
+  if (o.losses && o.step) stepv = (uint32_t)*o.step;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int r0 = tile * PD_ROWS;
+    pwd_load_x0(p, r0, tid, L.xa);
+    __syncthreads();
+    // xa -> xb -> xa -> xb
+    pwd_chain3(p, L.xa, L.xb, L.xa, L.xb, wave, lane);
+    {  // conv4 + ReLU: wave = 32 of the 128 channels, both row tiles
+      f32x4 bf[8];
+      pwd_frags<false>(p.w[3], 64, 64, 32 * wave, lane, bf);
+      const float bias = p.b[3][32 * wave + r];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        f32x16 acc = {};
+        acc = mfma_rows_x_wt<64>(L.xb + 32 * t * PD_S, PD_S, bf, acc, lane);
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          L.y4[(32 * t + acc_row(e, lane)) * PD_S4 + 32 * wave + r] =
+              act_fwd(acc[e] + bias, ACT_RELU);
+      }
+    }
+    __syncthreads();
+    {  // max over the channels, first index on ties: 4 lanes x 32 channels
+      const int row = tid >> 2, q = tid & 3;
+      const float* y = &L.y4[row * PD_S4 + 32 * q];
+      float best = y[0];
+      int bi = 32 * q;
+#pragma unroll 8
+      for (int c = 1; c < 32; ++c) {
+        const float v = y[c];
+        if (beats(v, best)) { best = v; bi = 32 * q + c; }
+      }
+#pragma unroll
+      for (int m = 1; m < 4; m <<= 1) {
+        const float ov = __shfl_xor(best, m);
+        const int oi = __shfl_xor(bi, m);
+        const bool up = q & m;  // this lane holds the higher channels
+        const float lo_v = up ? ov : best, hi_v = up ? best : ov;
+        const int lo_i = up ? oi : bi, hi_i = up ? bi : oi;
+        const bool t = beats(hi_v, lo_v);
+        best = t ? hi_v : lo_v;
+        bi = t ? hi_i : lo_i;
+      }
+      const long long g = (long long)r0 + row;
+      if (q == 0) {
+        float l0 = 0.f, l1 = 0.f, l2 = 0.f;
+        if (g < M) {
+          o.out[g] = best;
+          o.argc[g] = bi;
+          if (o.losses) {
+            // make_D_label(random=True), one label per point (utils/utils.py:22-31)
+            const float z = best;
+            const float sg = 1.f / (1.f + expf(-z));
+            const float sp = log1pf(expf(-fabsf(z)));
+            if (g < p.n0) {
+              const float y0 = o.soft0 ? o.soft0[g]
+                                       : 0.7f + 0.35f * rng_uniform(o.seed, stepv, RNG_LABEL_GT,
+                                                                    (uint32_t)g);
+              l1 = fmaxf(z, 0.f) - z * y0 + sp;
+              o.dout_d[g] = 0.5f * (sg - y0) / (float)p.n0;
+              if (o.soft_out) o.soft_out[g] = y0;
+            } else {
+              const long long j = g - p.n0;
+              const float y1 = o.soft1 ? o.soft1[j]
+                                       : 0.305f * rng_uniform(o.seed, stepv, RNG_LABEL_NOGT,
+                                                              (uint32_t)j);
+              l2 = fmaxf(z, 0.f) - z * y1 + sp;
+              l0 = fmaxf(z, 0.f) - z + sp;  // against label 1 (the generator's term)
+              o.dout_d[g] = 0.5f * (sg - y1) / (float)p.n1;
+              if (o.dout_adv) o.dout_adv[j] = (sg - 1.f) / (float)p.n1;
+              if (o.soft_out) o.soft_out[g] = y1;
+            }
+          }
+        }
+        L.lt[0][row] = l0;
+        L.lt[1][row] = l1;
+        L.lt[2][row] = l2;
+      }
+    }
+    __syncthreads();
+    if (o.losses && wave == 0) {
+      const float a0 = wave_sum(L.lt[0][lane]), a1 = wave_sum(L.lt[1][lane]),
+                  a2 = wave_sum(L.lt[2][lane]);
+      if (lane == 0) {
+        o.partial[3 * (size_t)tile + 0] = a0;
+        o.partial[3 * (size_t)tile + 1] = a1;
+        o.partial[3 * (size_t)tile + 2] = a2;
+      }
+    }
+    // the next tile's x0 goes to xa (last read before conv4's barrier), lt is
+    // rewritten after three more barriers
+  }
+  if (!o.losses) return;
+  // the last workgroup to arrive sums the tiles' terms in tile order (whichever
+  // workgroup that is, the order and so the bits are the same)
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    const unsigned t = atomicAdd(o.ticket, 1u);
+    L.last = t == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!L.last || wave != 0) return;
+  __threadfence();
+  float a[3] = {0.f, 0.f, 0.f};
+  for (int t = lane; t < ntiles; t += 64)
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      a[k] += __uint_as_float(__hip_atomic_load(
+          reinterpret_cast<const unsigned*>(o.partial) + 3 * (size_t)t + k, __ATOMIC_RELAXED,
+          __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+  for (int k = 0; k < 3; ++k) a[k] = wave_sum(a[k]);
+  if (lane == 0) {
+    const float adv = p.n1 ? a[0] / (float)p.n1 : 0.f;
+    const float dgt = p.n0 ? 0.5f * (a[1] / (float)p.n0) : 0.f;
+    const float dng = p.n1 ? 0.5f * (a[2] / (float)p.n1) : 0.f;
+    o.losses[0] = adv;        // loss_adv
+    o.losses[1] = dgt + dng;  // loss_D
+    o.losses[2] = dgt;
+    o.losses[3] = dng;
+    *o.ticket = 0u;  // ready for the next launch
+  }
+}
+
+// ---------------------------------------------------------------------------
+// backward
+// ---------------------------------------------------------------------------
+struct PwdBwdLds {
+  alignas(16) float x[4][PD_ROWS * PD_S];  // x0..x3
+  alignas(16) float da[PD_ROWS * PD_S];    // unit gradients, alternating
+  alignas(16) float db[PD_ROWS * PD_S];
+  float sv[PD_ROWS];  // D's dout of the row (0: dead row or past the end)
+  float av[PD_ROWS];  // lambda_adv dout_adv (no-GT rows)
+  int ac[PD_ROWS];    // argc, -1 for a dead row
+};
+
+// acc += (s dz)^T x over the tile's rows in row order: 32 x 32 (o, k) tile
+__device__ __forceinline__ f32x16 pwd_wgrad(const float* dz, const float* sv, const float* x,
+                                            int o0, int k0, f32x16 acc, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+#pragma unroll 8
+  for (int t = 0; t < 32; ++t) {
+    const int row = 2 * t + h;
+    acc = mfma32(dz[row * PD_S + o0 + r] * sv[row], x[row * PD_S + k0 + r], acc);
+  }
+  return acc;
+}
+
+// the data gradient of one layer: out = (in W) masked by relu'(y) (y = NULL: none)
+__device__ __forceinline__ void pwd_dgrad(const float* in, float* out, const float* y,
+                                          const f32x4 (&bf)[8], int wave, int lane) {
+  const int r = lane & 31, oc = 32 * (wave & 1), rt = wave >> 1;
+  f32x16 acc = {};
+  acc = mfma_rows_x_wt<64>(in + 32 * rt * PD_S, PD_S, bf, acc, lane);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int i = (32 * rt + acc_row(e, lane)) * PD_S + oc + r;
+    out[i] = (!y || y[i] > 0.f) ? acc[e] : 0.f;
+  }
+}
+
+// The whole backward of a row is linear in one scalar, so one unit chain per
+// row (gradient 1 at channel argc) serves both uses: the weight gradients scale
+// it by D's dout (sv), the no-GT rows' input gradient by lambda_adv dout_adv.
+__global__ void __launch_bounds__(PD_T, 1) k_pwd_bwd(PwdNet p, PwdBwdArgs a, int ntiles) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  PwdBwdLds& L = *reinterpret_cast<PwdBwdLds*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31;
+  const long long M = (long long)p.n0 + p.n1;
+  const int wo = 32 * (wave >> 1), wk = 32 * (wave & 1);  // this wave's (o, k) tile
+  f32x16 g1 = {}, g2 = {}, g3 = {}, g4a = {}, g4b = {};
+  float bsum = 0.f;  // wave 0: db3, wave 1: db2, wave 2: db1 (lane = channel)
+  float b4sum = 0.f;  // waves 2, 3: db4 of channel tid - 128
+  const bool want_dx = a.dlogits && a.dout_adv;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int r0 = tile * PD_ROWS;
+    pwd_load_x0(p, r0, tid, L.x[0]);
+    if (tid < PD_ROWS) {
+      const long long g = (long long)r0 + tid;
+      const bool live = g < M && a.out[g] > 0.f;  // relu'(0) = 0: a dead row gets nothing
+      L.sv[tid] = live ? a.dout_d[g] : 0.f;
+      L.av[tid] = (live && want_dx && g >= p.n0) ? a.lambda_adv * a.dout_adv[g - p.n0] : 0.f;
+      L.ac[tid] = live ? (a.argc[g] & 127) : -1;  // a channel of conv4 whatever the buffer holds
+    }
+    __syncthreads();
+    pwd_chain3(p, L.x[0], L.x[1], L.x[2], L.x[3], wave, lane);
+    if (a.x_out) {  // uniform over the grid
+#pragma unroll 4
+      for (int j = 0; j < PD_ROWS * 64 / PD_T; ++j) {
+        const int e = tid + PD_T * j, row = e >> 6, k = e & 63;
+        const long long g = (long long)r0 + row;
+        if (g < M)
+          for (int l = 0; l < 3; ++l)
+            a.x_out[((size_t)l * M + g) * 64 + k] = L.x[l + 1][row * PD_S + k];
+      }
+    }
+    // conv4: the gradient reaches channel argc only.  dW4 += onehot(argc) s x3
+    {
+      const int o = 32 * wave + r, h = lane >> 5;
+#pragma unroll 8
+      for (int t = 0; t < 32; ++t) {
+        const int row = 2 * t + h;
+        const float av = L.ac[row] == o ? L.sv[row] : 0.f;
+        g4a = mfma32(av, L.x[3][row * PD_S + r], g4a);
+        g4b = mfma32(av, L.x[3][row * PD_S + 32 + r], g4b);
+      }
+    }
+    if (wave >= 2) {
+      const int c = tid - 128;
+      for (int row = 0; row < PD_ROWS; ++row) b4sum += L.ac[row] == c ? L.sv[row] : 0.f;
+    }
+    // unit dz3 = W4[argc] relu'(x3)
+#pragma unroll
+    for (int j = 0; j < PD_ROWS * 64 / PD_T; ++j) {
+      const int e = tid + PD_T * j, row = e >> 6, k = e & 63;
+      const int c = L.ac[row];
+      L.da[row * PD_S + k] = (c >= 0 && L.x[3][row * PD_S + k] > 0.f) ? p.w[3][c * 64 + k] : 0.f;
+    }
+    f32x4 bf[8];
+    pwd_frags_t(p.w[2], 64, 64, wk, lane, bf);
+    __syncthreads();
+    // conv3
+    g3 = pwd_wgrad(L.da, L.sv, L.x[2], wo, wk, g3, lane);
+    if (wave == 0)
+      for (int row = 0; row < PD_ROWS; ++row) bsum += L.sv[row] * L.da[row * PD_S + lane];
+    pwd_dgrad(L.da, L.db, L.x[2], bf, wave, lane);
+    pwd_frags_t(p.w[1], 64, 64, wk, lane, bf);
+    __syncthreads();
+    // conv2
+    g2 = pwd_wgrad(L.db, L.sv, L.x[1], wo, wk, g2, lane);
+    if (wave == 1)
+      for (int row = 0; row < PD_ROWS; ++row) bsum += L.sv[row] * L.db[row * PD_S + lane];
+    pwd_dgrad(L.db, L.da, L.x[1], bf, wave, lane);
+    __syncthreads();
+    // conv1
+    g1 = pwd_wgrad(L.da, L.sv, L.x[0], wo, wk, g1, lane);
+    if (wave == 2)
+      for (int row = 0; row < PD_ROWS; ++row) bsum += L.sv[row] * L.da[row * PD_S + lane];
+    const bool dx_tile = want_dx && (long long)r0 + PD_ROWS > p.n0;  // uniform over the workgroup
+    if (dx_tile) {
+      pwd_frags_t(p.w[0], p.ncls, p.ncls, wk, lane, bf);
+      pwd_dgrad(L.da, L.db, nullptr, bf, wave, lane);
+    }
+    __syncthreads();
+    if (dx_tile) {  // through the input transform, written to the no-GT rows only
+      const int row = tid >> 2, q = tid & 3;
+      const long long g = (long long)r0 + row;
+      const float s = L.av[row];
+      float dy[16], y[16];
+      float sum = 0.f, dot = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int c = q + 4 * i;
+        dy[i] = c < p.ncls ? L.db[row * PD_S + c] * s : 0.f;
+        y[i] = L.x[0][row * PD_S + c];
+        sum += dy[i];
+        dot += dy[i] * y[i];
+      }
+      sum += __shfl_xor(sum, 1);
+      sum += __shfl_xor(sum, 2);
+      dot += __shfl_xor(dot, 1);
+      dot += __shfl_xor(dot, 2);
+      if (g >= p.n0 && g < M) {
+        float* dst = a.dlogits + (size_t)g * a.ldd;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int c = q + 4 * i;
+          float d = dy[i];
+          if (p.t1 == PCADV_PWD_LOG_SOFTMAX) d = dy[i] - expf(y[i]) * sum;
+          if (p.t1 == PCADV_PWD_SOFTMAX) d = y[i] * (dy[i] - dot);
+          if (c < p.ncls) dst[c] = d;
+        }
+      }
+    }
+    __syncthreads();  // x[0], sv and the gradient buffers are free for the next tile
+  }
+  float* slab = a.slabs + (size_t)blockIdx.x * SL_N;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int ro = acc_row(e, lane);
+    slab[SL_W1 + (wo + ro) * 64 + wk + r] = g1[e];
+    slab[SL_W2 + (wo + ro) * 64 + wk + r] = g2[e];
+    slab[SL_W3 + (wo + ro) * 64 + wk + r] = g3[e];
+    slab[SL_W4 + (32 * wave + ro) * 64 + r] = g4a[e];
+    slab[SL_W4 + (32 * wave + ro) * 64 + 32 + r] = g4b[e];
+  }
+  if (wave == 0) slab[SL_B3 + lane] = bsum;
+  if (wave == 1) slab[SL_B2 + lane] = bsum;
+  if (wave == 2) slab[SL_B1 + lane] = bsum;
+  if (wave >= 2) slab[SL_B4 + tid - 128] = b4sum;
+}
+
+struct PwdGrads {
+  float* dw[4];
+  float* db[4];
+};
+
+// the slabs summed in workgroup order
+__global__ void __launch_bounds__(256) k_pwd_bwd_finish(const float* __restrict__ slabs, int nslabs,
+                                                        int ncls, PwdGrads g) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= SL_N) return;
+  float s = 0.f;
+  for (int i = 0; i < nslabs; ++i) s += slabs[(size_t)i * SL_N + e];
+  if (e < SL_W2) {
+    const int o = e >> 6, k = e & 63;
+    if (k < ncls) g.dw[0][o * ncls + k] = s;
+  } else if (e < SL_W3) {
+    g.dw[1][e - SL_W2] = s;
+  } else if (e < SL_W4) {
+    g.dw[2][e - SL_W3] = s;
+  } else if (e < SL_B1) {
+    g.dw[3][e - SL_W4] = s;
+  } else if (e < SL_B2) {
+    g.db[0][e - SL_B1] = s;
+  } else if (e < SL_B3) {
+    g.db[1][e - SL_B2] = s;
+  } else if (e < SL_B4) {
+    g.db[2][e - SL_B3] = s;
+  } else {
+    g.db[3][e - SL_B4] = s;
+  }
+}
+
+int pwd_tiles(long long rows) { return (int)((rows + PD_ROWS - 1) / PD_ROWS); }
+int pwd_grid(int ntiles, int max_wg, int dflt) {
+  const int cap = max_wg > 0 ? max_wg : dflt;
+  return ntiles < cap ? ntiles : cap;
+}
+size_t pwd_partial_bytes(int ntiles) { return ((size_t)ntiles * 3 * 4 + 255) / 256 * 256; }
+
+int pwd_check(const pcadv_pwdisc_args* a, const char* what, PwdNet& p) {
+  PC_REQUIRE(a, "%s: args is NULL", what);
+  PC_REQUIRE(a->ncls >= 2 && a->ncls <= 64, "%s: ncls = %d, expected 2..64", what, a->ncls);
+  PC_REQUIRE(a->n0 >= 0 && a->n1 >= 0 && (long long)a->n0 + a->n1 >= 1 &&
+                 (long long)a->n0 + a->n1 <= 0x7fffffffLL - PD_ROWS,
+             "%s: row counts n0 = %d, n1 = %d", what, a->n0, a->n1);
+  PC_REQUIRE(a->ld >= a->ncls, "%s: row stride ld = %lld < ncls = %d", what, (long long)a->ld,
+             a->ncls);
+  PC_REQUIRE(a->t0 >= 0 && a->t0 <= 2 && a->t1 >= 0 && a->t1 <= 2,
+             "%s: transforms (%d, %d): PCADV_PWD_NONE / _SOFTMAX / _LOG_SOFTMAX", what, a->t0,
+             a->t1);
+  PC_REQUIRE(a->max_workgroups >= 0, "%s: max_workgroups = %d", what, a->max_workgroups);
+  PC_REQUIRE(a->logits && a->out && a->argc, "%s: logits, out and argc are required", what);
+  for (int i = 0; i < 4; ++i) {
+    PC_REQUIRE(a->w[i] && a->b[i], "%s: conv%d's weight and bias are required", what, i + 1);
+    PC_REQUIRE(i == 0 || ((uintptr_t)a->w[i] & 15) == 0, "%s: conv%d's weight is not 16-B aligned",
+               what, i + 1);
+    p.w[i] = a->w[i];
+    p.b[i] = a->b[i];
+  }
+  p.logits = a->logits;
+  p.ld = a->ld;
+  p.ncls = a->ncls;
+  p.n0 = a->n0;
+  p.n1 = a->n1;
+  p.t0 = a->t0;
+  p.t1 = a->t1;
+  return PCADV_OK;
+}
+
+template <typename K>
+int pwd_lds(K kernel, size_t bytes, const char* what) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: %zu bytes of LDS refused", what, bytes);
+    return PCADV_EHIP;
+  }
+  return PCADV_OK;
+}
+
+}  // namespace
+
+size_t pwdisc_workspace_bytes(long long rows, int max_wg) {
+  if (rows < 1) return 0;
+  const int nt = pwd_tiles(rows);
+  return WS_HEAD + pwd_partial_bytes(nt) + (size_t)pwd_grid(nt, max_wg, PD_BWD_WG) * SL_N * 4;
+}
+
+int launch_pwdisc_fwd(const pcadv_pwdisc_args* a, hipStream_t s) {
+  PwdNet p;
+  if (int rc = pwd_check(a, "pcadv_pwdisc_forward", p)) return rc;
+  const long long rows = (long long)a->n0 + a->n1;
+  const int nt = pwd_tiles(rows);
+  PwdFwdOut o = {};
+  o.out = a->out;
+  o.argc = a->argc;
+  if (a->losses) {
+    PC_REQUIRE(a->dout_d, "pcadv_pwdisc_forward: losses need dout_d");
+    const bool drawn = (a->n0 > 0 && !a->soft0) || (a->n1 > 0 && !a->soft1);
+    PC_REQUIRE(!drawn || a->step_count, "pcadv_pwdisc_forward: device-drawn labels need step_count");
+    PC_REQUIRE(a->workspace && a->workspace_bytes >= pwdisc_workspace_bytes(rows, a->max_workgroups),
+               "pcadv_pwdisc_forward: workspace of %zu bytes, need %zu", a->workspace_bytes,
+               pwdisc_workspace_bytes(rows, a->max_workgroups));
+    o.losses = a->losses;
+    o.soft0 = a->soft0;
+    o.soft1 = a->soft1;
+    o.soft_out = a->soft_out;
+    o.seed = a->rng_seed;
+    o.step = a->step_count;
+    o.dout_d = a->dout_d;
+    o.dout_adv = a->dout_adv;
+    o.ticket = reinterpret_cast<unsigned*>(a->workspace);
+    o.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + WS_HEAD);
+  }
+  // Once per process, as every launcher of this library does (set outside any
+  // stream capture by the first eager call).  The attribute belongs to the
+  // current device's copy of the kernel: a process that drives a second device
+  // would have to set it there too (data parallelism runs one process per GPU).
+  static int once = pwd_lds(k_pwd_fwd, sizeof(PwdFwdLds), "k_pwd_fwd");
+  if (once) return once;
+  hipLaunchKernelGGL(k_pwd_fwd, dim3(pwd_grid(nt, a->max_workgroups, PD_FWD_WG)), dim3(PD_T),
+                     sizeof(PwdFwdLds), s, p, o, nt);
+  PC_HIP_CHECK_LAUNCH("k_pwd_fwd");
+  return PCADV_OK;
+}
+
+int launch_pwdisc_bwd(const pcadv_pwdisc_args* a, hipStream_t s) {
+  PwdNet p;
+  if (int rc = pwd_check(a, "pcadv_pwdisc_backward", p)) return rc;
+  const long long rows = (long long)a->n0 + a->n1;
+  const int nt = pwd_tiles(rows);
+  PC_REQUIRE(a->dout_d, "pcadv_pwdisc_backward: dout_d is required");
+  PwdGrads g;
+  for (int i = 0; i < 4; ++i) {
+    PC_REQUIRE(a->dw[i] && a->db[i], "pcadv_pwdisc_backward: conv%d's gradients are required", i + 1);
+    g.dw[i] = a->dw[i];
+    g.db[i] = a->db[i];
+  }
+  PC_REQUIRE(!a->dlogits || a->ldd >= a->ncls, "pcadv_pwdisc_backward: dlogits stride %lld < ncls",
+             (long long)a->ldd);
+  PC_REQUIRE(a->workspace && a->workspace_bytes >= pwdisc_workspace_bytes(rows, a->max_workgroups),
+             "pcadv_pwdisc_backward: workspace of %zu bytes, need %zu", a->workspace_bytes,
+             pwdisc_workspace_bytes(rows, a->max_workgroups));
+  PwdBwdArgs b;
+  b.out = a->out;
+  b.argc = a->argc;
+  b.dout_d = a->dout_d;
+  b.dout_adv = a->dout_adv;
+  b.lambda_adv = a->lambda_adv;
+  b.dlogits = a->dlogits;
+  b.ldd = a->ldd;
+  b.x_out = a->x_out;
+  b.slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + WS_HEAD +
+                                     pwd_partial_bytes(nt));
+  static int once = pwd_lds(k_pwd_bwd, sizeof(PwdBwdLds), "k_pwd_bwd");  // see launch_pwdisc_fwd
+  if (once) return once;
+  const int grid = pwd_grid(nt, a->max_workgroups, PD_BWD_WG);
+  hipLaunchKernelGGL(k_pwd_bwd, dim3(grid), dim3(PD_T), sizeof(PwdBwdLds), s, p, b, nt);
+  PC_HIP_CHECK_LAUNCH("k_pwd_bwd");
+  hipLaunchKernelGGL(k_pwd_bwd_finish, dim3((SL_N + 255) / 256), dim3(256), 0, s, b.slabs, grid,
+                     a->ncls, g);
+  PC_HIP_CHECK_LAUNCH("k_pwd_bwd_finish");
+  return PCADV_OK;
+}
+
+}  // namespace pcadv

@@ -1,13 +1,29 @@
-"""Drop-in DeepConvDiscNet backed by the pcadv linear kernels
-(models/discriminator.py:30-51): five 1x1 Conv1d layers on B x C x 1 with
-LeakyReLU(0.2), then Linear(64, output_dim).  Same state_dict as the reference."""
+"""Drop-in discriminators of models/discriminator.py, same state_dicts as the
+reference.
+
+DeepConvDiscNet (:30-51), backed by the pcadv linear kernels: five 1x1 Conv1d
+layers on B x C x 1 with LeakyReLU(0.2), then Linear(64, output_dim).
+
+PointwiseDiscNet (:53-79), the per-point discriminator of run_training_seg
+(utils/trainer.py:849-1026): conv1..conv4 + ReLU and the max over the 128
+channels, one logit per point, fused in csrc/pwdisc.hip (pwdisc_forward /
+pwdisc_backward below are the thin calls into it)."""
 from __future__ import annotations
 
+import ctypes
+
+import torch
 import torch.nn as nn
 
+from . import _lib
+from ._lib import PWD_LOG_SOFTMAX, PWD_NONE, PWD_SOFTMAX, check, stream_ptr
+from ._lib import ptr as _vp
 from .ops import ACT_LRELU, ACT_NONE, LinearFunction
 
-__all__ = ["DeepConvDiscNet"]
+__all__ = ["DeepConvDiscNet", "PointwiseDiscNet", "pwdisc_forward", "pwdisc_backward",
+           "pwdisc_workspace", "PWD_NONE", "PWD_SOFTMAX", "PWD_LOG_SOFTMAX"]
+
+PWD_MAX_DIM = 64  # input channels the fused kernels take (the MFMA's padded K)
 
 
 class DeepConvDiscNet(nn.Module):
@@ -26,3 +42,179 @@ class DeepConvDiscNet(nn.Module):
         for conv in (self.conv1, self.conv2, self.conv3, self.conv4, self.conv5):
             h = LinearFunction.apply(h, conv.weight, conv.bias, ACT_LRELU, None, 0.0)
         return LinearFunction.apply(h, self.fc.weight, self.fc.bias, ACT_NONE, None, 0.0)
+
+
+def _f32(t, name, numel=None):
+    if t.device.type != "cuda":
+        raise ValueError(f"{name}: pcadv ops run on the HIP device only (got {t.device})")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name}: expected {numel} elements, got {t.numel()}")
+    return t
+
+
+def pwdisc_workspace(rows, device, max_workgroups=0, zero=True):
+    """The workspace the forward and the backward of `rows` points share.  Only a
+    forward with losses needs it zeroed (its ticket); the backward writes its
+    slabs before it reads them, and a forward without losses takes ws=None."""
+    n = max(int(_lib.load().pcadv_pwdisc_workspace_bytes(int(rows), int(max_workgroups))), 256)
+    return (torch.zeros if zero else torch.empty)(n, device=device, dtype=torch.uint8)
+
+
+def _args(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups):
+    rows = n0 + n1
+    if logits.dim() != 2 or logits.shape[0] != rows or logits.shape[1] < ncls \
+            or logits.stride(1) != 1:
+        raise ValueError(f"logits: expected point-major ({rows}, >= {ncls}) rows, "
+                         f"got {tuple(logits.shape)} with strides {logits.stride()}")
+    if logits.device.type != "cuda" or logits.dtype != torch.float32:
+        raise TypeError("logits: expected torch.float32 on the HIP device")
+    if not 2 <= ncls <= PWD_MAX_DIM:
+        raise ValueError(f"ncls: the fused discriminator takes 2..{PWD_MAX_DIM} channels, got {ncls}")
+    shapes = [(64, ncls), (64,), (64, 64), (64,), (64, 64), (64,), (128, 64), (128,)]
+    a = _lib.PwdiscArgs()
+    for i, (p, shp) in enumerate(zip(params, shapes)):
+        n = 1
+        for d in shp:
+            n *= d
+        _f32(p, f"D parameter {i}", n)
+        if i % 2 == 0:
+            a.w[i // 2] = p.data_ptr()
+        else:
+            a.b[i // 2] = p.data_ptr()
+    a.logits, a.ld = _vp(logits), logits.stride(0) if rows > 1 else max(logits.stride(0), ncls)
+    a.ncls, a.n0, a.n1, a.t0, a.t1 = ncls, n0, n1, int(t0), int(t1)
+    a.out, a.argc = _vp(_f32(out, "out", rows)), _vp(argc)
+    if argc.dtype != torch.int32 or argc.numel() != rows or argc.device.type != "cuda":
+        raise TypeError("argc: expected int32 of one element per row on the HIP device")
+    a.max_workgroups = int(max_workgroups)
+    if ws is not None:
+        a.workspace, a.workspace_bytes = _vp(ws), ws.numel()
+    return a
+
+
+def pwdisc_forward(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, *, losses=None,
+                   soft0=None, soft1=None, soft_out=None, seed=0, step_count=None, dout_d=None,
+                   dout_adv=None, max_workgroups=0):
+    """pcadv_pwdisc_forward on the current stream (include/pcadv.h): out, argc
+    and, with `losses` (4 floats), the BCE terms with dout_d / dout_adv."""
+    a = _args(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups)
+    if losses is not None:
+        a.losses = _vp(_f32(losses, "losses", 4))
+        a.soft0 = _vp(None if soft0 is None else _f32(soft0, "soft0", n0))
+        a.soft1 = _vp(None if soft1 is None else _f32(soft1, "soft1", n1))
+        a.soft_out = _vp(None if soft_out is None else _f32(soft_out, "soft_out", n0 + n1))
+        a.rng_seed = int(seed)
+        a.step_count = _vp(step_count)
+        a.dout_d = _vp(_f32(dout_d, "dout_d", n0 + n1))
+        a.dout_adv = _vp(None if dout_adv is None else _f32(dout_adv, "dout_adv", n1))
+    check(_lib.load().pcadv_pwdisc_forward(ctypes.byref(a), stream_ptr()), "pcadv_pwdisc_forward")
+
+
+def pwdisc_backward(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, dout_d, grads, *,
+                    dout_adv=None, lambda_adv=1.0, dlogits=None, max_workgroups=0, x_out=None):
+    """pcadv_pwdisc_backward on the current stream: `grads` (eight
+    parameter-shaped tensors, state_dict order) are written, and rows
+    [n0, n0 + n1) of `dlogits` when it and dout_adv are given.  x_out
+    (3, n0 + n1, 64), optional, receives the recomputed x1..x3."""
+    a = _args(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups)
+    a.dout_d = _vp(_f32(dout_d, "dout_d", n0 + n1))
+    a.dout_adv = _vp(None if dout_adv is None else _f32(dout_adv, "dout_adv", n1))
+    a.lambda_adv = float(lambda_adv)
+    for i, (g, p) in enumerate(zip(grads, params)):
+        _f32(g, f"D gradient {i}", p.numel())
+        if i % 2 == 0:
+            a.dw[i // 2] = g.data_ptr()
+        else:
+            a.db[i // 2] = g.data_ptr()
+    if x_out is not None:
+        a.x_out = _vp(_f32(x_out, "x_out", 3 * (n0 + n1) * 64))
+    if dlogits is not None:
+        if dlogits.dim() != 2 or dlogits.shape[0] != n0 + n1 or dlogits.shape[1] < ncls \
+                or dlogits.stride(1) != 1 or dlogits.dtype != torch.float32 \
+                or dlogits.device.type != "cuda":
+            raise ValueError("dlogits: expected point-major float32 rows like logits")
+        a.dlogits, a.ldd = _vp(dlogits), max(dlogits.stride(0), ncls)
+    check(_lib.load().pcadv_pwdisc_backward(ctypes.byref(a), stream_ptr()), "pcadv_pwdisc_backward")
+
+
+def _point_major(x):
+    """x (B, C, N) as point-major rows (B * N, ld) without a copy when it is a
+    permuted view of point-major storage (what PointNetSeg.forward returns)."""
+    B, C, N = x.shape
+    xt = x.permute(0, 2, 1)  # (B, N, C)
+    if not xt.is_contiguous():
+        xt = xt.contiguous()
+    return xt.reshape(B * N, C)
+
+
+class _PointwiseDisc(torch.autograd.Function):
+    """x (B, C, N) -> (B * N,) logits: the fused forward, and the fused backward
+    scaled per row by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        B, C, N = x.shape
+        rows = _point_major(x.detach())
+        M = B * N
+        out = torch.empty(M, device=x.device)
+        argc = torch.empty(M, device=x.device, dtype=torch.int32)
+        ps = [p.detach().contiguous() for p in params]
+        pwdisc_forward(rows, C, 0, M, PWD_NONE, PWD_NONE, ps, out, argc, None)
+        ctx.save_for_backward(rows, out, argc, *ps)
+        ctx.dims = (B, C, N)
+        ctx.mark_non_differentiable(argc)
+        return out, argc
+
+    @staticmethod
+    def backward(ctx, dout, _dargc):
+        rows, out, argc, *ps = ctx.saved_tensors
+        B, C, N = ctx.dims
+        M = B * N
+        d = dout.reshape(M).contiguous().float()
+        grads = [torch.empty_like(p) for p in ps]
+        need_dx = ctx.needs_input_grad[0]
+        dl = torch.empty(M, C, device=rows.device) if need_dx else None
+        ws = pwdisc_workspace(M, rows.device, zero=False)
+        pwdisc_backward(rows, C, 0, M, PWD_NONE, PWD_NONE, ps, out, argc, ws, d, grads,
+                        dout_adv=d if need_dx else None, lambda_adv=1.0, dlogits=dl)
+        dx = dl.view(B, N, C).permute(0, 2, 1) if need_dx else None
+        return (dx, *grads)
+
+
+class PointwiseDiscNet(nn.Module):
+    """models/discriminator.py:53-79.  forward(x: B x input_dim x N) ->
+    B*N/input_pts x input_pts (B x N when N == input_pts)."""
+
+    def __init__(self, input_pts, input_dim):
+        super().__init__()
+        if not 2 <= int(input_dim) <= PWD_MAX_DIM:
+            raise ValueError(f"input_dim: the fused discriminator takes 2..{PWD_MAX_DIM} "
+                             f"channels, got {input_dim}")
+        if int(input_pts) < 1:
+            raise ValueError(f"input_pts: expected a positive point count, got {input_pts}")
+        self.input_pts = int(input_pts)
+        self.input_dim = int(input_dim)
+        self.conv1 = nn.Conv1d(input_dim, 64, 1)
+        self.conv2 = nn.Conv1d(64, 64, 1)
+        self.conv3 = nn.Conv1d(64, 64, 1)
+        self.conv4 = nn.Conv1d(64, 128, 1)
+
+    def check_input(self, x):
+        if x.dim() != 3 or x.shape[1] != self.input_dim:
+            raise ValueError(f"x: expected B x {self.input_dim} x N, got {tuple(x.shape)}")
+        if (x.shape[0] * x.shape[2]) % self.input_pts:
+            raise ValueError(f"x: {x.shape[0]} x {x.shape[2]} points do not fill rows of "
+                             f"input_pts = {self.input_pts}")
+        if not x.is_floating_point() or x.dtype != torch.float32:
+            raise TypeError(f"x: expected torch.float32, got {x.dtype}")
+
+    def forward(self, x):
+        self.check_input(x)
+        if x.device.type != "cuda":
+            raise ValueError(f"x: pcadv ops run on the HIP device only (got {x.device})")
+        out, _ = _PointwiseDisc.apply(x, *[p for _, p in self.named_parameters()])
+        return out.view(-1, self.input_pts)

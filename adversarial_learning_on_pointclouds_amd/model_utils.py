@@ -6,7 +6,7 @@ import sys
 import torch
 from torch.nn import init
 
-from .discriminator import DeepConvDiscNet
+from .discriminator import DeepConvDiscNet, PointwiseDiscNet
 from .pointnet import PointNetCls
 
 
@@ -54,9 +54,9 @@ def init_weights(net, init_type, init_gain=1.0, verbose=True):
 
 
 def load_models(mode, device, args):
-    """utils/model_utils.py:60-140 for the hot path's modes 'cls' and 'disc' and
-    the segmentation row's 'seg'.
-    The segmentation / stacked discriminators are outside this build's scope."""
+    """utils/model_utils.py:60-140 for the hot path's modes 'cls' and 'disc', the
+    segmentation row's 'seg' and its per-point discriminator 'disc_seg'.
+    The dual / stacked discriminators are outside this build's scope."""
     if mode == "cls":
         model = PointNetCls(k=40, feature_transform=False).to(device)
         try:
@@ -80,7 +80,10 @@ def load_models(mode, device, args):
             print("Loading pretrained cls model ...")
             model.load_state_dict(torch.load(args.checkpoint, map_location=device,
                                              weights_only=True))
-    elif mode in ("seg_regu", "disc_seg", "disc_dual", "disc_stack"):
+    elif mode == "disc_seg":  # :113-115, PointwiseDiscNet (run_training_seg's D)
+        model = PointwiseDiscNet(input_pts=args.input_pts, input_dim=args.disc_indim)
+        model = init_net(model, device, init_type=args.init_disc)
+    elif mode in ("seg_regu", "disc_dual", "disc_stack"):
         raise NotImplementedError(f"mode {mode!r} is outside the adversarial cls hot path")
     else:
         raise ValueError("Invalid mode {}!".format(mode))

@@ -40,7 +40,8 @@ from . import _lib
 from ._lib import check, stream_ptr
 from .step import _step_tensor, set_optimizer_step
 
-__all__ = ["PointNetSeg", "SegTrainStep", "seg_cross_entropy", "seg_forward", "seg_backward"]
+__all__ = ["PointNetSeg", "SegTrainStep", "SegAdvTrainStep", "seg_cross_entropy", "seg_forward",
+           "seg_backward"]
 
 _LOC = 960                       # x1..x5 widths 64 + 128 + 128 + 128 + 512
 PRECISIONS = ("fp32", "bf16x3")
@@ -708,3 +709,217 @@ class SegTrainStep:
     def sync_optimizer_state(self):
         if self.optimizer is not None:
             set_optimizer_step(self.optimizer, float(self.step_count.item()))
+
+
+def _flat_state(model, optimizer, dev):
+    """The model's parameters as views of one flat f32 buffer, their .grad views
+    of one flat gradient buffer, and flat Adam moments handed to `optimizer` as
+    its state (what SegTrainStep does for the generator).  Returns (param, grad,
+    m, v, grad_views, t0, numel, offsets)."""
+    named = list(model.named_parameters())
+    offs, n = [], 0
+    for _, p in named:
+        offs.append(n)
+        n += (p.numel() + 63) // 64 * 64  # 256-B aligned views
+    param, grad = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    m, v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    views, t0 = [], 0
+    for (_, p), o in zip(named, offs):
+        k = p.numel()
+        param[o:o + k].copy_(p.detach().reshape(-1))
+        st = optimizer.state.get(p) if optimizer is not None else None
+        if st and "exp_avg" in st:  # Adam state the optimizer already holds carries over
+            m[o:o + k].copy_(st["exp_avg"].detach().reshape(-1))
+            v[o:o + k].copy_(st["exp_avg_sq"].detach().reshape(-1))
+            t0 = max(t0, int(float(st.get("step", 0))))
+        p.data = param[o:o + k].view_as(p)
+        p.grad = grad[o:o + k].view_as(p)
+        views.append(p.grad)
+    if optimizer is not None:
+        for (_, p), o in zip(named, offs):
+            k = p.numel()
+            optimizer.state[p] = {"step": _step_tensor(optimizer, p, t0),
+                                  "exp_avg": m[o:o + k].view_as(p),
+                                  "exp_avg_sq": v[o:o + k].view_as(p)}
+    return param, grad, m, v, views, t0, n, offs
+
+
+def _adam_hyper(optimizer, lr, betas, eps):
+    if optimizer is not None:
+        g = optimizer.param_groups[0]
+        return float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"])
+    return float(lr), tuple(betas), float(eps)
+
+
+class SegAdvTrainStep:
+    """One iteration of run_training_seg (utils/trainer.py:873-966) with
+    ImagePool(0), PointNetSeg + PointwiseDiscNet and two Adams, as native
+    launches on one stream, capturable into a HIP graph:
+
+      weight-plane split; seg_forward on the 2B clouds [GT; no-GT] (PointNetSeg
+      has no batch statistics: the reference's two forwards); pcadv_row_ce on the
+      GT rows (dlogits rows [0, B N), scale lambda_seg); the fused D forward on
+      softmax(GT) / log_softmax(no-GT) (trainer.py:901,914) with loss_adv, loss_D
+      and their derivatives; the fused D backward (D's gradients from both of its
+      terms, and the no-GT rows of dlogits from lambda_adv loss_adv through the
+      frozen D); seg_backward; the two Adam updates.
+
+    The no-GT rows feed the adversarial term and D's own term from one forward
+    (D is frozen in the first and its input detached in the second, so the three
+    reference forwards compute the same values).  Parameters, gradients and Adam
+    moments of G and of D are flat buffers handed to the torch modules and
+    optimizers as views.  D always runs in f32; `precision` is the generator's.
+    Soft labels: explicit (soft_gt / soft_nogt, one per point) or drawn on the
+    device keyed by (seed, the generator's step counter, row)."""
+
+    def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
+                 lambda_adv=0.01, lr=1e-4, lr_D=1e-4, betas=(0.9, 0.999), eps=1e-8, device="cuda",
+                 precision=None, seed=0, keep_activations=False):
+        from .discriminator import PointwiseDiscNet
+        self.lib = _lib.load()
+        if not isinstance(model, PointNetSeg) or not isinstance(model_D, PointwiseDiscNet):
+            raise TypeError("SegAdvTrainStep: expected a PointNetSeg and a PointwiseDiscNet")
+        if model_D.input_dim != model.output_dim:
+            raise ValueError(f"model_D takes {model_D.input_dim} channels, the generator predicts "
+                             f"{model.output_dim} classes")
+        self.precision = _check_precision(precision or getattr(model, "precision", "fp32"))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("SegAdvTrainStep runs on the HIP device only")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device, self.model, self.model_D = dev, model, model_D
+        self.optimizer, self.optimizer_D = optimizer, optimizer_D
+        self.lambda_seg, self.lambda_adv, self.seed = float(lambda_seg), float(lambda_adv), int(seed)
+        self.lr, self.betas, self.eps = _adam_hyper(optimizer, lr, betas, eps)
+        self.lr_D, self.betas_D, self.eps_D = _adam_hyper(optimizer_D, lr_D, betas, eps)
+        (self.param, self.grad, self.m, self.v, self.grad_views, t0, self.numel,
+         offs) = _flat_state(model, optimizer, dev)
+        (self.d_param, self.d_grad, self.d_m, self.d_v, self.d_grad_views, t0d, self.d_numel,
+         _) = _flat_state(model_D, optimizer_D, dev)
+        self.step_count = torch.full((1,), t0, device=dev, dtype=torch.int32)
+        self.step_count_D = torch.full((1,), t0d, device=dev, dtype=torch.int32)
+        self.params = [p for _, p in model.named_parameters()]
+        self.d_params = [p for _, p in model_D.named_parameters()]
+        n = self.numel
+        self.wph = torch.empty(n, device=dev, dtype=torch.bfloat16)
+        self.wpl = torch.empty(n, device=dev, dtype=torch.bfloat16)
+        self.wplanes = [(self.wph[o:o + p.numel()], self.wpl[o:o + p.numel()])
+                        for p, o in zip(self.params, offs)]
+        # [loss_seg, loss_adv, loss_D, loss_D's GT part, its no-GT part]
+        self.loss_buf = torch.zeros(5, device=dev)
+        self.keep_activations = bool(keep_activations)
+        self.fw = self.d_out = None
+        self._ws = None
+
+    def __call__(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
+                 apply_adam=True):
+        from .discriminator import PWD_LOG_SOFTMAX, PWD_SOFTMAX, pwdisc_backward, pwdisc_forward, \
+            pwdisc_workspace
+        B, N, _ = pts_gt.shape
+        _check_dev(pts_gt, "pts_gt")
+        _check_dev(pts_nogt, "pts_nogt", shape=(B, N, 3))
+        if seg.shape != (B, N) or seg.dtype != torch.int64 or not seg.is_contiguous():
+            raise ValueError("seg: expected contiguous int64 (B, N)")
+        if (B * N) % self.model_D.input_pts:
+            raise ValueError(f"{B} x {N} points do not fill rows of model_D.input_pts = "
+                             f"{self.model_D.input_pts}")
+        M = B * N
+        wpl = None
+        if _PLANES:  # every weight's planes (fp32 mode reads conv6's only)
+            _engine().split(self.param, self.wph, self.wpl)
+            wpl = self.wplanes
+        pts = torch.cat([pts_gt, pts_nogt])
+        cls = torch.cat([cls_gt.float().reshape(B, 1, 16), cls_nogt.float().reshape(B, 1, 16)])
+        fw = seg_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
+        ncls = fw["dims"][2]
+        logits = fw["logits"]
+        d = torch.empty(2 * M, ncls, device=self.device)
+        ws = _ws(self.lib.pcadv_row_ce_workspace_bytes(M), self.device)
+        check(self.lib.pcadv_row_ce(_p(logits), ncls, _p(seg), M, ncls, self.lambda_seg,
+                                    _p(self.loss_buf), _p(d), _p(ws), ws.numel(), stream_ptr()),
+              "pcadv_row_ce")
+        if self._ws is None or self._ws[0] != M:
+            self._ws = (M, pwdisc_workspace(2 * M, self.device))
+        dws = self._ws[1]
+        out = torch.empty(2 * M, device=self.device)
+        argc = torch.empty(2 * M, device=self.device, dtype=torch.int32)
+        dout_d = torch.empty(2 * M, device=self.device)
+        dout_adv = torch.empty(M, device=self.device)
+        pwdisc_forward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, out, argc,
+                       dws, losses=self.loss_buf[1:5],
+                       soft0=None if soft_gt is None else soft_gt.reshape(M),
+                       soft1=None if soft_nogt is None else soft_nogt.reshape(M), seed=self.seed,
+                       step_count=self.step_count, dout_d=dout_d, dout_adv=dout_adv)
+        pwdisc_backward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, out, argc,
+                        dws, dout_d, self.d_grad_views, dout_adv=dout_adv,
+                        lambda_adv=self.lambda_adv, dlogits=d)
+        seg_backward(fw, d, None, out=self.grad_views)
+        if self.keep_activations:
+            self.fw, self.d_out = fw, out
+        if apply_adam:
+            self.adam()
+        return self.losses
+
+    def adam(self):
+        """optimizer.step() and optimizer_D.step() (trainer.py:965-966)."""
+        check(self.lib.pcadv_adam(_p(self.param), _p(self.grad), _p(self.m), _p(self.v), self.numel,
+                                  _p(self.step_count), self.lr, self.betas[0], self.betas[1],
+                                  self.eps, stream_ptr()), "pcadv_adam")
+        check(self.lib.pcadv_adam(_p(self.d_param), _p(self.d_grad), _p(self.d_m), _p(self.d_v),
+                                  self.d_numel, _p(self.step_count_D), self.lr_D, self.betas_D[0],
+                                  self.betas_D[1], self.eps_D, stream_ptr()), "pcadv_adam")
+
+    @property
+    def losses(self):
+        """[loss_seg, loss_adv, loss_D] (the trainers' loss-ring interface)."""
+        return self.loss_buf[:3]
+
+    def graph_state(self):
+        """What a captured iteration's warm-up changes (restored after it)."""
+        return [self.param, self.m, self.v, self.step_count, self.d_param, self.d_m, self.d_v,
+                self.step_count_D]
+
+    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None):
+        """One HIP graph of a step reading the given resident buffers: a single
+        stream, no parallel branches (state is restored to what it was before
+        the warm-up)."""
+        saved = [t.clone() for t in self.graph_state()]
+        args = (pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt)
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self(*args)
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self(*args)
+        torch.cuda.synchronize()
+        for dst, src in zip(self.graph_state(), saved):
+            dst.copy_(src)
+        return g
+
+    def sync_hyper(self):
+        """lr / betas / eps as the optimizers hold them now (a graph captured
+        before keeps the old values)."""
+        self.lr, self.betas, self.eps = _adam_hyper(self.optimizer, self.lr, self.betas, self.eps)
+        self.lr_D, self.betas_D, self.eps_D = _adam_hyper(self.optimizer_D, self.lr_D, self.betas_D,
+                                                          self.eps_D)
+
+    def sync_optimizer_state(self):
+        if self.optimizer is not None:
+            set_optimizer_step(self.optimizer, float(self.step_count.item()))
+        if self.optimizer_D is not None:
+            set_optimizer_step(self.optimizer_D, float(self.step_count_D.item()))
+
+    def after_eager(self):
+        """After iterations run by the torch optimizers on the same (flat)
+        parameters and moments: take over their step counts and hand the
+        modules' .grad back to the flat gradient buffers."""
+        for opt, cnt in ((self.optimizer, self.step_count), (self.optimizer_D, self.step_count_D)):
+            steps = [int(float(st["step"])) for st in opt.state.values() if st] if opt else []
+            if steps:
+                cnt.fill_(max(steps))
+        for ps, views in ((self.params, self.grad_views), (self.d_params, self.d_grad_views)):
+            for p, gv in zip(ps, views):
+                p.grad = gv

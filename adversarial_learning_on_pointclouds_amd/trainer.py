@@ -1216,3 +1216,144 @@ def run_training_pointnet_seg(trainloader_gt, trainloader_gt_iter, testloader, t
     train_logger.info("Max cat mIoU: {:.4f}, at epoch: {}".format(max_test_cat_iou, max_train_cat_epoch))
     train_logger.info("Max all mIoU: {:.4f}, at epoch: {}".format(max_test_all_iou, max_train_all_epoch))
     return max_test_accu, max_test_cat_iou, max_test_all_iou
+
+
+def _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, pool_gt, pool_nogt,
+                     args):
+    """The configuration SegAdvTrainStep implements (run_training_seg's fast path)."""
+    from .discriminator import PointwiseDiscNet
+    from .seg import PointNetSeg
+    if not (isinstance(model, PointNetSeg) and isinstance(model_D, PointwiseDiscNet)):
+        return False
+    if model_D.input_dim != model.output_dim or str(args.device).split(":")[0] != "cuda":
+        return False
+    for opt in (optimizer, optimizer_D):
+        if type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1:
+            return False
+        g = opt.param_groups[0]
+        if g.get("weight_decay", 0) or g.get("amsgrad") or g.get("maximize"):
+            return False
+    if type(gan_loss) is not torch.nn.BCEWithLogitsLoss or gan_loss.weight is not None \
+            or gan_loss.pos_weight is not None or gan_loss.reduction != "mean":
+        return False
+    if type(seg_loss) is not torch.nn.CrossEntropyLoss or seg_loss.weight is not None \
+            or seg_loss.reduction != "mean" or seg_loss.ignore_index >= 0 \
+            or seg_loss.label_smoothing != 0.0:
+        return False
+    return getattr(pool_gt, "pool_size", 1) == 0 and getattr(pool_nogt, "pool_size", 1) == 0
+
+
+def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, pool_gt, pool_nogt,
+                  pts, cls, seg, pts_nogt, cls_nogt, args):
+    """utils/trainer.py:881-966 through autograd over the same modules."""
+    optimizer.zero_grad()
+    optimizer_D.zero_grad()
+    for param in model_D.parameters():  # train G
+        param.requires_grad = False
+    pred, _ = model(pts, cls)
+    l_seg = seg_loss(pred, seg)
+    pred_gt_softmax = F.softmax(pred, dim=1)
+    pred_nogt, _ = model(pts_nogt, cls_nogt)
+    pred_nogt_softmax = F.log_softmax(pred_nogt, dim=1)
+    D_out = model_D(pred_nogt_softmax)
+    loss_adv = gan_loss(D_out, make_D_label(input=D_out, value=1, device=args.device, random=False))
+    (args.lambda_seg * l_seg + args.lambda_adv * loss_adv).backward()
+    for param in model_D.parameters():  # train D
+        param.requires_grad = True
+    loss_D_value = 0.0
+    for pool, x, value in ((pool_gt, pred_gt_softmax, 1), (pool_nogt, pred_nogt_softmax, 0)):
+        D_out = model_D(pool.query(x.detach()))
+        loss_D = 0.5 * gan_loss(D_out, make_D_label(input=D_out, value=value, device=args.device,
+                                                    random=True))
+        loss_D.backward()
+        loss_D_value += loss_D.item()
+    optimizer.step()
+    optimizer_D.step()
+    return [l_seg.item(), loss_adv.item(), loss_D_value]
+
+
+def run_training_seg(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetloader_nogt_iter,
+                     testloader, testdataset, model, model_D, gan_loss, seg_loss, optimizer,
+                     optimizer_D, history_pool_gt, history_pool_nogt, train_logger, test_logger,
+                     writer, args):
+    """utils/trainer.py:849-1026: adversarial segmentation with the per-point
+    discriminator.  With PointNetSeg + PointwiseDiscNet, two plain Adams,
+    CrossEntropyLoss + BCEWithLogitsLoss and ImagePool(0) on the HIP device,
+    every iteration whose two batches have the same shape is one
+    SegAdvTrainStep; any other configuration, and a ragged last batch, runs the
+    reference's body through autograd over the same modules."""
+    from .seg import SegAdvTrainStep
+    max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
+    max_train_epoch = max_train_cat_epoch = max_train_all_epoch = 0
+    fusable = _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                               history_pool_gt, history_pool_nogt, args)
+    step, eager_since = None, False
+    tb = getattr(args, "tensorboard", False) and writer is not None
+
+    def save(tag):
+        if step is not None:
+            step.sync_optimizer_state()
+        torch.save(model.state_dict(), os.path.join(args.exp_dir, "model_train_{}.pth".format(tag)))
+        torch.save(model_D.state_dict(), os.path.join(args.exp_dir, "modelD_train_{}.pth".format(tag)))
+
+    for i_iter in range(args.total_iterations):
+        model.train()
+        model_D.train()
+        batch, trainloader_gt_iter = _next(trainloader_gt, trainloader_gt_iter)
+        pts, cls, seg = batch
+        pts, cls, seg = pts.float().to(args.device), cls.float().to(args.device), \
+            seg.long().to(args.device)
+        batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
+        pts_nogt, cls_nogt = batch
+        pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
+        if fusable and pts.shape == pts_nogt.shape \
+                and (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0:
+            if step is None:
+                step = SegAdvTrainStep(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
+                                       lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
+                                       device=args.device, seed=int(getattr(args, "seed", 0) or 0))
+            elif eager_since:
+                step.after_eager()
+            eager_since = False
+            step.sync_hyper()
+            vals = step(pts.contiguous(), cls.contiguous(), seg.contiguous(),
+                        pts_nogt.contiguous(), cls_nogt.contiguous()).tolist()
+        else:
+            if step is not None:
+                step.sync_optimizer_state()
+            eager_since = True
+            vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                                 history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
+                                 cls_nogt, args)
+        train_logger.info('iter = {0:8d}/{1:8d} '
+                          'loss_seg = {2:.3f} '
+                          'loss_adv = {3:.3f} '
+                          'loss_D = {4:.3f} '.format(i_iter, args.total_iterations, *vals))
+        if tb:
+            writer.add_scalar('Loss/train_seg', vals[0], i_iter)
+            writer.add_scalar('Loss/train_adv', vals[1], i_iter)
+            writer.add_scalar('Loss/train_disc', vals[2], i_iter)
+        if i_iter % args.iter_test_epoch == 0:
+            save("epoch_{}".format(i_iter // args.iter_test_epoch))
+            accu, _, cat_iou, all_iou = run_testing_seg(
+                dataloader=testloader, dataset=testdataset, model=model, criterion=seg_loss,
+                logger=test_logger, test_iter=i_iter, writer=writer, args=args)
+            ep = i_iter // args.iter_test_epoch
+            if max_seg_accu < accu:
+                max_seg_accu, max_train_epoch = accu, ep
+                save("best")
+            if max_test_cat_iou < cat_iou:
+                max_test_cat_iou, max_train_cat_epoch = cat_iou, ep
+                save("best_cat_iou")
+            if max_test_all_iou < all_iou:
+                max_test_all_iou, max_train_all_epoch = all_iou, ep
+                save("best_all_iou")
+    if step is not None:
+        step.sync_optimizer_state()
+    train_logger.info("=========================")
+    train_logger.info("Max accuracy: {:.4f}, at epoch: {}".format(max_seg_accu, max_train_epoch))
+    train_logger.info("Max cat mIoU: {:.4f}, at epoch: {}".format(max_test_cat_iou, max_train_cat_epoch))
+    train_logger.info("Max all mIoU: {:.4f}, at epoch: {}".format(max_test_all_iou, max_train_all_epoch))
+    if tb:
+        writer.close()
+    return max_seg_accu, max_test_cat_iou, max_test_all_iou

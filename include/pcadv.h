@@ -657,6 +657,77 @@ int pcadv_adv_step_adam(const pcadv_adv_args* args, hipStream_t stream);
  * with or without Adam) and runs Adam at the advanced count. */
 int pcadv_cls_step(const pcadv_adv_args* args, hipStream_t stream);
 
+/* ---- PointwiseDiscNet of the adversarial segmentation step -----------------
+ * (models/discriminator.py:53-79, utils/trainer.py:849-1026, run_training_seg.)
+ * Additions to ABI 10 (nothing existing changes).
+ *
+ * logits [n0 + n1][ncls] point-major (row stride ld), 2 <= ncls <= 64.  Rows
+ * [0, n0) are the GT clouds' points and enter D through transform t0, rows
+ * [n0, n0 + n1) the no-GT clouds' through t1 (the reference: softmax and
+ * log_softmax, trainer.py:901,914).  w[i] / b[i]: conv1..conv4 ([64][ncls],
+ * [64][64], [64][64], [128][64]; conv2..conv4 16-B aligned).
+ *
+ * pcadv_pwdisc_forward, one launch: out[row] = max over the 128 channels of
+ * relu(conv4(..relu(conv1(x)))) on exact f32 MFMAs in k order, argc[row] its
+ * channel (the first on ties).  With losses != NULL also the iteration's
+ * three BCE-with-logits terms:
+ *   losses[0] = loss_adv = mean over the no-GT rows against label 1,
+ *   losses[2] = 0.5 mean over the GT rows against soft labels of U(0.7, 1.05),
+ *   losses[3] = 0.5 mean over the no-GT rows against soft labels of U(0, 0.305),
+ *   losses[1] = loss_D = losses[2] + losses[3],
+ * and their derivatives dout_d[n0 + n1] (loss_D's) and dout_adv[n1]
+ * (loss_adv's, optional).  The labels, one per point (make_D_label(random=
+ * True)), are soft0[n0] / soft1[n1] or, where those are NULL, drawn from Philox
+ * keyed by (rng_seed, *step_count, row); soft_out[n0 + n1] (optional) receives
+ * them.  The sums run in a fixed order (no floating-point atomics).  The first
+ * 256 bytes of the workspace are a ticket that must be zero when a forward
+ * with losses starts and is zero again when it ends: zero the workspace once.
+ *
+ * pcadv_pwdisc_backward, one launch and a fixed-order finish: recomputes
+ * x1..x3 (the forward's bits), routes the gradient to channel argc (none for a
+ * row whose out is 0) and writes dw[i] / db[i] = the gradients of
+ * sum_row dout_d[row] out[row], and, with dlogits and dout_adv given, the
+ * gradient of lambda_adv sum_j dout_adv[j] out[n0 + j] with respect to the
+ * no-GT rows' logits (through transform t1) into rows [n0, n0 + n1) of
+ * dlogits (row stride ldd; the other rows are not touched).  Reads out, argc.
+ * x_out (optional, [3][n0 + n1][64]) receives the recomputed x1..x3, whose signs
+ * are the ReLU masks the backward used (tests).
+ *
+ * max_workgroups: 0, or a cap on the persistent grids (tests).  The workspace
+ * (pcadv_pwdisc_workspace_bytes(n0 + n1, max_workgroups)) is shared by the two. */
+#define PCADV_PWD_NONE 0
+#define PCADV_PWD_SOFTMAX 1
+#define PCADV_PWD_LOG_SOFTMAX 2
+typedef struct pcadv_pwdisc_args {
+  const float* logits;
+  int64_t ld;
+  int ncls, n0, n1, t0, t1;
+  const float* w[4];
+  const float* b[4];
+  float* out;
+  int32_t* argc;
+  float* losses;
+  const float* soft0;
+  const float* soft1;
+  float* soft_out;
+  uint64_t rng_seed;
+  const int32_t* step_count;
+  float* dout_d;
+  float* dout_adv;
+  float lambda_adv;
+  float* dw[4];
+  float* db[4];
+  float* dlogits;
+  int64_t ldd;
+  int max_workgroups;
+  void* workspace;
+  size_t workspace_bytes;
+  float* x_out;
+} pcadv_pwdisc_args;
+size_t pcadv_pwdisc_workspace_bytes(int64_t rows, int max_workgroups);
+int pcadv_pwdisc_forward(const pcadv_pwdisc_args* args, hipStream_t stream);
+int pcadv_pwdisc_backward(const pcadv_pwdisc_args* args, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

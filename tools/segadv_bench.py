@@ -1,0 +1,132 @@
+"""Time of the adversarial segmentation step against the generator-only step
+on the same 32 clouds, both as replayed HIP graphs on seeded synthetic data:
+
+  adv: SegAdvTrainStep, B = 16 + 16 (GT + no-GT), N = 2048, PointNetSeg(50) +
+       PointwiseDiscNet(2048, 50), device-drawn labels
+  seg: SegTrainStep, B = 32, N = 2048, PointNetSeg(50)
+
+The difference is the cost of the discriminator (its fused forward with the
+BCE terms, its fused backward, the second Adam, the input concatenation),
+less the cross entropy of the 16 no-GT clouds that the adversarial step does
+not compute.  After a warm-up, `--rounds` rounds alternate `--steps` replays
+of each graph between device events; medians, spread and the per-kernel share
+are printed and written to profiles/segadv_bench.json.  Needs the MI355X.
+
+    python tools/segadv_bench.py [--rounds 7] [--steps 20] [--out profiles/segadv_bench.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def _inputs(rng, B, N):
+    pts = torch.from_numpy(rng.uniform(-1, 1, (B, N, 3)).astype(np.float32)).cuda()
+    cls = torch.from_numpy(np.eye(16, dtype=np.float32)[rng.integers(0, 16, B)][:, None, :]).cuda()
+    seg = torch.from_numpy(rng.integers(0, 50, (B, N))).cuda()
+    return pts, cls, seg
+
+
+def _time(graph, steps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        graph.replay()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def _d_alone(step, M, steps):
+    """The D launches alone (forward with losses, backward + finish) on a
+    logits-shaped input, as eager launches between device events (so each
+    figure includes the host's launch cost: an upper bound on the kernels)."""
+    from adversarial_learning_on_pointclouds_amd import discriminator as D
+    dev = step.device
+    lg = torch.randn(2 * M, 50, device=dev) * 2
+    out, argc = torch.empty(2 * M, device=dev), torch.empty(2 * M, device=dev, dtype=torch.int32)
+    dd, da = torch.empty(2 * M, device=dev), torch.empty(M, device=dev)
+    dl, ws = torch.empty(2 * M, 50, device=dev), D.pwdisc_workspace(2 * M, dev)
+    losses = torch.zeros(4, device=dev)
+
+    def fwd():
+        D.pwdisc_forward(lg, 50, M, M, D.PWD_SOFTMAX, D.PWD_LOG_SOFTMAX, step.d_params, out, argc,
+                         ws, losses=losses, seed=1, step_count=step.step_count, dout_d=dd,
+                         dout_adv=da)
+
+    def bwd():
+        D.pwdisc_backward(lg, 50, M, M, D.PWD_SOFTMAX, D.PWD_LOG_SOFTMAX, step.d_params, out, argc,
+                          ws, dd, step.d_grad_views, dout_adv=da, lambda_adv=0.01, dlogits=dl)
+    res = {}
+    for name, fn in (("d_forward_ms", fwd), ("d_backward_ms", bwd)):
+        fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(steps):
+            fn()
+        b.record()
+        b.synchronize()
+        res[name] = a.elapsed_time(b) / steps
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join("profiles", "segadv_bench.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("segadv_bench: no HIP device (the steps are timed on the MI355X only)")
+    import adversarial_learning_on_pointclouds_amd as pc
+    B, N = 16, 2048
+    rng = np.random.default_rng(0)
+    torch.manual_seed(0)
+    pts, cls, seg = _inputs(rng, 2 * B, N)
+    g_adv = pc.PointNetSeg(50).cuda()
+    d_adv = pc.PointwiseDiscNet(N, 50).cuda()
+    g_seg = pc.PointNetSeg(50).cuda()
+    g_seg.load_state_dict(g_adv.state_dict())
+    adv = pc.SegAdvTrainStep(g_adv, d_adv, lr=1e-4, lr_D=1e-4, lambda_adv=0.01, seed=5)
+    sup = pc.SegTrainStep(g_seg, lr=1e-4)
+    graphs = {
+        "adv": adv.capture_on(pts[:B].contiguous(), cls[:B].contiguous(), seg[:B].contiguous(),
+                              pts[B:].contiguous(), cls[B:].contiguous()),
+        "seg": sup.capture_on(pts, cls, seg),
+    }
+    for g in graphs.values():  # warm-up
+        _time(g, 5)
+    times = {k: [] for k in graphs}
+    for _ in range(a.rounds):
+        for k, g in graphs.items():
+            times[k].append(_time(g, a.steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "steps": a.steps,
+           "what": {"adv": "SegAdvTrainStep B=16+16 N=2048 fp32, graph replay",
+                    "seg": "SegTrainStep B=32 N=2048 fp32, graph replay"},
+           "adv_ms": {"median": med["adv"], "min": min(times["adv"]), "max": max(times["adv"]),
+                      "rounds": times["adv"]},
+           "seg_ms": {"median": med["seg"], "min": min(times["seg"]), "max": max(times["seg"]),
+                      "rounds": times["seg"]},
+           "d_cost_ms": med["adv"] - med["seg"],
+           "d_share_of_adv_step": (med["adv"] - med["seg"]) / med["adv"],
+           "losses_last": [float(x) for x in adv.losses.tolist()]}
+    out.update(_d_alone(adv, B * N, a.steps))
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"adv_ms": med["adv"], "seg_ms": med["seg"], "d_cost_ms": out["d_cost_ms"],
+                      "d_share": out["d_share_of_adv_step"], "d_forward_ms": out["d_forward_ms"],
+                      "d_backward_ms": out["d_backward_ms"]}))
+
+
+if __name__ == "__main__":
+    main()
