@@ -8,7 +8,8 @@ Drop-in counterparts of the reference's models and training loop
 fused native step AdvTrainStep; PointNetSeg (models/pointnet.py:261-317) with
 its native training step SegTrainStep; PointwiseDiscNet
 (models/discriminator.py:53-79) and the adversarial segmentation step
-SegAdvTrainStep (run_training_seg); run_training_semi; the HDF5 datasets of
+SegAdvTrainStep (run_training_seg, and run_training_seg_semi with its
+pseudo-label term); run_training_semi; the HDF5 datasets of
 dataset/modelNetData.py and dataset/shapeNetData.py without h5py, with a
 device-resident batch loader (dataset.DeviceCloudLoader) and native test
 passes over it (evaluate.ClsEvaluator / SegEvaluator).  All compute runs in

@@ -217,6 +217,9 @@ SIGNATURES = {
     "pcadv_pwdisc_workspace_bytes": (_sz, [_i64, _i]),
     "pcadv_pwdisc_forward": (_i, [ctypes.POINTER(PwdiscArgs), _vp]),
     "pcadv_pwdisc_backward": (_i, [ctypes.POINTER(PwdiscArgs), _vp]),
+    "pcadv_row_semi_ce_workspace_bytes": (_sz, [_i]),
+    "pcadv_row_semi_ce": (_i, [_vp, _i64, _vp, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz,
+                               _vp]),
 }
 
 _lib = None

@@ -770,11 +770,20 @@ class SegAdvTrainStep:
     moments of G and of D are flat buffers handed to the torch modules and
     optimizers as views.  D always runs in f32; `precision` is the generator's.
     Soft labels: explicit (soft_gt / soft_nogt, one per point) or drawn on the
-    device keyed by (seed, the generator's step counter, row)."""
+    device keyed by (seed, the generator's step counter, row).
+
+    semi=True adds run_training_seg_semi's term (utils/trainer.py:1999-2024):
+    after the D backward, pcadv_row_semi_ce on the no-GT rows adds lambda_semi
+    times the cross entropy of the points whose D output is above semi_th
+    against their own argmax to those rows of dlogits (D receives nothing from
+    it).  It needs model_D.input_pts == N, as the reference's mask does.  The
+    term's loss and the number of kept points are `losses_semi[2]` and `kept`;
+    `losses` stays [loss_seg, loss_adv, loss_D].  A captured graph has `semi`
+    baked in: capture one graph per value."""
 
     def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
                  lambda_adv=0.01, lr=1e-4, lr_D=1e-4, betas=(0.9, 0.999), eps=1e-8, device="cuda",
-                 precision=None, seed=0, keep_activations=False):
+                 precision=None, seed=0, keep_activations=False, lambda_semi=1.0, semi_th=0.8):
         from .discriminator import PointwiseDiscNet
         self.lib = _lib.load()
         if not isinstance(model, PointNetSeg) or not isinstance(model_D, PointwiseDiscNet):
@@ -791,6 +800,7 @@ class SegAdvTrainStep:
         self.device, self.model, self.model_D = dev, model, model_D
         self.optimizer, self.optimizer_D = optimizer, optimizer_D
         self.lambda_seg, self.lambda_adv, self.seed = float(lambda_seg), float(lambda_adv), int(seed)
+        self.lambda_semi, self.semi_th = float(lambda_semi), float(semi_th)
         self.lr, self.betas, self.eps = _adam_hyper(optimizer, lr, betas, eps)
         self.lr_D, self.betas_D, self.eps_D = _adam_hyper(optimizer_D, lr_D, betas, eps)
         (self.param, self.grad, self.m, self.v, self.grad_views, t0, self.numel,
@@ -806,14 +816,16 @@ class SegAdvTrainStep:
         self.wpl = torch.empty(n, device=dev, dtype=torch.bfloat16)
         self.wplanes = [(self.wph[o:o + p.numel()], self.wpl[o:o + p.numel()])
                         for p, o in zip(self.params, offs)]
-        # [loss_seg, loss_adv, loss_D, loss_D's GT part, its no-GT part]
-        self.loss_buf = torch.zeros(5, device=dev)
+        # [loss_seg, loss_adv, loss_D, loss_D's GT part, its no-GT part, loss_semi]
+        self.loss_buf = torch.zeros(6, device=dev)
+        self.kept_buf = torch.zeros(1, device=dev, dtype=torch.int32)
         self.keep_activations = bool(keep_activations)
-        self.fw = self.d_out = None
+        self.fw = self.d_out = self.semi_labels = None
         self._ws = None
+        self._semi_stale = False
 
     def __call__(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
-                 apply_adam=True):
+                 apply_adam=True, semi=False):
         from .discriminator import PWD_LOG_SOFTMAX, PWD_SOFTMAX, pwdisc_backward, pwdisc_forward, \
             pwdisc_workspace
         B, N, _ = pts_gt.shape
@@ -824,6 +836,9 @@ class SegAdvTrainStep:
         if (B * N) % self.model_D.input_pts:
             raise ValueError(f"{B} x {N} points do not fill rows of model_D.input_pts = "
                              f"{self.model_D.input_pts}")
+        if semi and self.model_D.input_pts != N:
+            raise ValueError(f"semi=True: model_D.input_pts = {self.model_D.input_pts} is not the "
+                             f"clouds' {N} points (the reference's mask indexes (B, N))")
         M = B * N
         wpl = None
         if _PLANES:  # every weight's planes (fp32 mode reads conv6's only)
@@ -854,9 +869,27 @@ class SegAdvTrainStep:
         pwdisc_backward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, out, argc,
                         dws, dout_d, self.d_grad_views, dout_adv=dout_adv,
                         lambda_adv=self.lambda_adv, dlogits=d)
+        labels = None
+        if semi:
+            if self.keep_activations:
+                labels = torch.empty(M, device=self.device, dtype=torch.int32)
+            sws = _ws(self.lib.pcadv_row_semi_ce_workspace_bytes(M), self.device)
+            check(self.lib.pcadv_row_semi_ce(_p(logits, M * ncls), ncls, _p(out, M), M, ncls,
+                                             self.semi_th, self.lambda_semi, _p(d, M * ncls), ncls,
+                                             None if labels is None else _p(labels),
+                                             _p(self.loss_buf, 5), _p(self.kept_buf), _p(sws),
+                                             sws.numel(), stream_ptr()),
+                  "pcadv_row_semi_ce")
+            self._semi_stale = True
+        elif self._semi_stale:
+            # the first step without the term after one with it: loss_semi and K
+            # back to 0 (a step that never ran the term launches nothing for it)
+            self.loss_buf[5:].zero_()
+            self.kept_buf.zero_()
+            self._semi_stale = False
         seg_backward(fw, d, None, out=self.grad_views)
         if self.keep_activations:
-            self.fw, self.d_out = fw, out
+            self.fw, self.d_out, self.semi_labels = fw, out, labels
         if apply_adam:
             self.adam()
         return self.losses
@@ -875,17 +908,30 @@ class SegAdvTrainStep:
         """[loss_seg, loss_adv, loss_D] (the trainers' loss-ring interface)."""
         return self.loss_buf[:3]
 
+    @property
+    def losses_semi(self):
+        """[loss_seg, loss_adv, loss_semi, loss_D] of the last step (loss_semi is
+        0 for a step without the term, or with no point kept)."""
+        return self.loss_buf[[0, 1, 5, 2]]
+
+    @property
+    def kept(self):
+        """The number of no-GT points the last step's semi term kept (device
+        int32; 0 for a step without the term)."""
+        return self.kept_buf[0]
+
     def graph_state(self):
         """What a captured iteration's warm-up changes (restored after it)."""
         return [self.param, self.m, self.v, self.step_count, self.d_param, self.d_m, self.d_v,
                 self.step_count_D]
 
-    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None):
+    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
+                   semi=False):
         """One HIP graph of a step reading the given resident buffers: a single
         stream, no parallel branches (state is restored to what it was before
-        the warm-up)."""
+        the warm-up).  `semi` is baked into the graph."""
         saved = [t.clone() for t in self.graph_state()]
-        args = (pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt)
+        args = (pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True, semi)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):

@@ -1,7 +1,8 @@
 """Training / evaluation loops with the reference's signatures
 (utils/trainer.py:30-69 run_testing, :72-143 run_testing_seg, :222-308
 run_training_pointnet_cls, :310-400 run_training_pointnet_seg, :403-608
-run_training, :611-847 run_training_semi).
+run_training, :611-847 run_training_semi, :849-1026 run_training_seg,
+:1903-2121 run_training_seg_semi).
 
 run_training runs each iteration through the fused native step
 (AdvTrainStep: one C-ABI call, no per-op Python) whenever the configuration is
@@ -1342,6 +1343,140 @@ def run_training_seg(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targ
             if max_seg_accu < accu:
                 max_seg_accu, max_train_epoch = accu, ep
                 save("best")
+            if max_test_cat_iou < cat_iou:
+                max_test_cat_iou, max_train_cat_epoch = cat_iou, ep
+                save("best_cat_iou")
+            if max_test_all_iou < all_iou:
+                max_test_all_iou, max_train_all_epoch = all_iou, ep
+                save("best_all_iou")
+    if step is not None:
+        step.sync_optimizer_state()
+    train_logger.info("=========================")
+    train_logger.info("Max accuracy: {:.4f}, at epoch: {}".format(max_seg_accu, max_train_epoch))
+    train_logger.info("Max cat mIoU: {:.4f}, at epoch: {}".format(max_test_cat_iou, max_train_cat_epoch))
+    train_logger.info("Max all mIoU: {:.4f}, at epoch: {}".format(max_test_all_iou, max_train_all_epoch))
+    if tb:
+        writer.close()
+    return max_seg_accu, max_test_cat_iou, max_test_all_iou
+
+
+def _seg_semi_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, semi_loss, pool_gt,
+                   pool_nogt, pts, cls, seg, pts_nogt, cls_nogt, semi, args):
+    """utils/trainer.py:1956-2061 through autograd over the same modules; `semi`
+    is the iteration's (args.semi_start > 0 and i_iter > args.semi_start)."""
+    optimizer.zero_grad()
+    optimizer_D.zero_grad()
+    for param in model_D.parameters():  # train G
+        param.requires_grad = False
+    pred, _ = model(pts, cls)
+    l_seg = seg_loss(pred, seg)
+    pred_gt_softmax = F.softmax(pred, dim=1)
+    pred_nogt, _ = model(pts_nogt, cls_nogt)
+    pred_nogt_softmax = F.log_softmax(pred_nogt, dim=1)
+    D_out = model_D(pred_nogt_softmax)
+    loss_adv = gan_loss(D_out, make_D_label(input=D_out, value=1, device=args.device, random=False))
+    loss = args.lambda_seg * l_seg + args.lambda_adv * loss_adv
+    loss_semi_value = 0.0
+    if semi:
+        ignore = (D_out <= args.semi_TH).squeeze(1)  # (B N / input_pts, input_pts) on (B, N)
+        semi_gt = torch.argmax(pred_nogt.detach(), dim=1)
+        semi_gt[ignore] = 255
+        if not bool(ignore.all()):  # semi_ratio != 0.0
+            l_semi = semi_loss(pred_nogt, semi_gt)
+            loss_semi_value = l_semi.item()
+            loss = loss + args.lambda_semi * l_semi
+    loss.backward()
+    for param in model_D.parameters():  # train D
+        param.requires_grad = True
+    loss_D_value = 0.0
+    for pool, x, value in ((pool_gt, pred_gt_softmax, 1), (pool_nogt, pred_nogt_softmax, 0)):
+        D_out = model_D(pool.query(x.detach()))
+        loss_D = 0.5 * gan_loss(D_out, make_D_label(input=D_out, value=value, device=args.device,
+                                                    random=True))
+        loss_D.backward()
+        loss_D_value += loss_D.item()
+    optimizer.step()  # the reference steps G before D's part: D is frozen there, the same values
+    optimizer_D.step()
+    return [l_seg.item(), loss_adv.item(), loss_semi_value, loss_D_value]
+
+
+def run_training_seg_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                          targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
+                          seg_loss, semi_loss, optimizer, optimizer_D, history_pool_gt,
+                          history_pool_nogt, train_logger, test_logger, writer, args):
+    """utils/trainer.py:1903-2121: run_training_seg plus, for i_iter >
+    args.semi_start (> 0), lambda_semi x semi_loss(pred_nogt, argmax(pred_nogt))
+    over the no-GT points the frozen discriminator scores above args.semi_TH
+    (the rest are ignore_index 255).  In run_training_seg's fused configuration,
+    with CrossEntropyLoss(ignore_index=255) as semi_loss and model_D.input_pts
+    equal to the clouds' points, every iteration whose two batches have the
+    same shape is one SegAdvTrainStep (semi=True from iteration semi_start + 1);
+    anything else, and a ragged batch, runs the reference's body through
+    autograd over the same modules.  Checkpoints: epoch_{}, best_cat_iou and
+    best_all_iou (the reference saves none by accuracy here)."""
+    from .seg import SegAdvTrainStep
+    max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
+    max_train_epoch = max_train_cat_epoch = max_train_all_epoch = 0
+    fusable = _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                               history_pool_gt, history_pool_nogt, args) and _semi_fusable(semi_loss)
+    step, eager_since = None, False
+    tb = getattr(args, "tensorboard", False) and writer is not None
+
+    def save(tag):
+        if step is not None:
+            step.sync_optimizer_state()
+        torch.save(model.state_dict(), os.path.join(args.exp_dir, "model_train_{}.pth".format(tag)))
+        torch.save(model_D.state_dict(), os.path.join(args.exp_dir, "modelD_train_{}.pth".format(tag)))
+
+    for i_iter in range(args.total_iterations):
+        model.train()
+        model_D.train()
+        batch, trainloader_gt_iter = _next(trainloader_gt, trainloader_gt_iter)
+        pts, cls, seg = batch
+        pts, cls, seg = pts.float().to(args.device), cls.float().to(args.device), \
+            seg.long().to(args.device)
+        batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
+        pts_nogt, cls_nogt = batch
+        pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
+        semi = args.semi_start > 0 and i_iter > args.semi_start
+        if fusable and pts.shape == pts_nogt.shape and model_D.input_pts == pts.shape[1]:
+            if step is None:
+                step = SegAdvTrainStep(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
+                                       lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
+                                       device=args.device, seed=int(getattr(args, "seed", 0) or 0),
+                                       lambda_semi=float(getattr(args, "lambda_semi", 1.0)),
+                                       semi_th=float(getattr(args, "semi_TH", 0.8)))
+            elif eager_since:
+                step.after_eager()
+            eager_since = False
+            step.sync_hyper()
+            step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
+                 cls_nogt.contiguous(), semi=semi)
+            vals = step.losses_semi.tolist()
+        else:
+            if step is not None:
+                step.sync_optimizer_state()
+            eager_since = True
+            vals = _seg_semi_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                                  semi_loss, history_pool_gt, history_pool_nogt, pts, cls, seg,
+                                  pts_nogt, cls_nogt, semi, args)
+        train_logger.info('iter = {0:8d}/{1:8d} '
+                          'loss_seg = {2:.3f} '
+                          'loss_adv = {3:.3f} '
+                          'loss semi = {4:.3f} '
+                          'loss_D = {5:.3f}'.format(i_iter, args.total_iterations, *vals))
+        if tb:
+            writer.add_scalar('Loss/train_seg', vals[0], i_iter)
+            writer.add_scalar('Loss/train_adv', vals[1], i_iter)
+            writer.add_scalar('Loss/train_disc', vals[3], i_iter)
+        if i_iter % args.iter_test_epoch == 0:
+            ep = i_iter // args.iter_test_epoch
+            save("epoch_{}".format(ep))
+            accu, _, cat_iou, all_iou = run_testing_seg(
+                dataloader=testloader, dataset=testdataset, model=model, criterion=seg_loss,
+                logger=test_logger, test_iter=i_iter, writer=writer, args=args)
+            if max_seg_accu < accu:
+                max_seg_accu, max_train_epoch = accu, ep
             if max_test_cat_iou < cat_iou:
                 max_test_cat_iou, max_train_cat_epoch = cat_iou, ep
                 save("best_cat_iou")

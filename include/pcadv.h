@@ -728,6 +728,33 @@ size_t pcadv_pwdisc_workspace_bytes(int64_t rows, int max_workgroups);
 int pcadv_pwdisc_forward(const pcadv_pwdisc_args* args, hipStream_t stream);
 int pcadv_pwdisc_backward(const pcadv_pwdisc_args* args, hipStream_t stream);
 
+/* ---- The semi-supervised term of run_training_seg_semi ----------------------
+ * (utils/trainer.py:1999-2024.)  Additions to ABI 10 (nothing existing changes).
+ *
+ * logits [M][ncls] (row stride ld >= ncls, 2 <= ncls <= 64) are the no-GT
+ * rows' predictions, d_out [M] D's raw per-point output on them.  Row r is
+ * KEPT iff !(d_out[r] <= semi_th) (a value equal to the threshold is ignored,
+ * as semi_ignore_mask = D_out <= semi_TH does).  Its pseudo-label is the FIRST
+ * index of the row's maximum (torch.argmax); labels_out (optional, int32 [M])
+ * receives it for a kept row and 255 for an ignored one.  With K kept rows:
+ *   *loss = (1/K) sum over kept rows of (logsumexp(row) - max(row)), 0 if K = 0
+ *           (CrossEntropyLoss(ignore_index=255) of the rows against their own
+ *           argmax; the reference logs 0 when every point is ignored),
+ *   dlogits[r][c] += scale / K (softmax(row)[c] - [c == label])  on kept rows,
+ *   *kept_out = K (optional, int32).
+ * The gradient is ADDED (row stride ldd >= ncls): the no-GT rows already hold
+ * the adversarial term's gradient.  Ignored rows, columns >= ncls, and
+ * everything when K = 0 are not written at all.  K and the loss are summed in a
+ * fixed order (no floating-point atomics): the same inputs leave the same bits.
+ * Two launches, no host synchronisation; every workspace slot is written before
+ * it is read in each call, so the workspace needs no zeroing, ever.  Calls
+ * sharing a workspace must be ordered on one stream. */
+size_t pcadv_row_semi_ce_workspace_bytes(int M);
+int pcadv_row_semi_ce(const float* logits, int64_t ld, const float* d_out, int M, int ncls,
+                      float semi_th, float scale, float* dlogits, int64_t ldd,
+                      int32_t* labels_out, float* loss, int32_t* kept_out, void* workspace,
+                      size_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,11 @@ of each graph between device events; medians, spread and the per-kernel share
 are printed and written to profiles/segadv_bench.json.  Needs the MI355X.
 
     python tools/segadv_bench.py [--rounds 7] [--steps 20] [--out profiles/segadv_bench.json]
+
+--semi times instead the adversarial step with run_training_seg_semi's term
+(semi=True, a threshold that keeps about half the no-GT points) against the
+same step without it, alternated the same way, into
+profiles/segadv_semi_bench.json.
 """
 import argparse
 import json
@@ -77,14 +82,80 @@ def _d_alone(step, M, steps):
     return res
 
 
+def _semi(a):
+    """--semi: the adversarial step with run_training_seg_semi's term against
+    the same step without it, two graphs over the same inputs and equal models,
+    alternated.  Both Adams run at lr 0, so the parameters and with them the
+    kept share (the threshold is the median of the first step's no-GT D
+    outputs) stay what they are over the replays; the launches are the same."""
+    import adversarial_learning_on_pointclouds_amd as pc
+    B, N = 16, 2048
+    rng = np.random.default_rng(0)
+    torch.manual_seed(0)
+    pts, cls, seg = _inputs(rng, 2 * B, N)
+    args = (pts[:B].contiguous(), cls[:B].contiguous(), seg[:B].contiguous(),
+            pts[B:].contiguous(), cls[B:].contiguous())
+    steps = {}
+    for k in ("plain", "semi"):
+        g, d = pc.PointNetSeg(50).cuda(), pc.PointwiseDiscNet(N, 50).cuda()
+        if steps:
+            g.load_state_dict(steps["plain"].model.state_dict())
+            d.load_state_dict(steps["plain"].model_D.state_dict())
+        steps[k] = pc.SegAdvTrainStep(g, d, lr=0.0, lr_D=0.0, lambda_adv=0.01, seed=5,
+                                      keep_activations=(k == "plain"))
+    steps["plain"](*args)
+    th = float(steps["plain"].d_out[B * N:].median().item())
+    steps["plain"].keep_activations, steps["plain"].fw, steps["plain"].d_out = False, None, None
+    steps["semi"].semi_th = th
+    graphs = {"plain": steps["plain"].capture_on(*args),
+              "semi": steps["semi"].capture_on(*args, semi=True)}
+    for g in graphs.values():  # warm-up
+        _time(g, 5)
+    times = {k: [] for k in graphs}
+    for _ in range(a.rounds):
+        for k, g in graphs.items():
+            times[k].append(_time(g, a.steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    diffs = [s - p for s, p in zip(times["semi"], times["plain"])]
+    kept = int(steps["semi"].kept.item())
+    out = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "steps": a.steps,
+           "what": "SegAdvTrainStep B=16+16 N=2048 fp32, graph replay, semi=True against "
+                   "semi=False, alternated, lr 0",
+           "semi_th": th, "kept": kept, "kept_share": kept / float(B * N),
+           "plain_ms": {"median": med["plain"], "min": min(times["plain"]),
+                        "max": max(times["plain"]), "rounds": times["plain"]},
+           "semi_ms": {"median": med["semi"], "min": min(times["semi"]), "max": max(times["semi"]),
+                       "rounds": times["semi"]},
+           "semi_cost_us": {"median_of_medians": 1e3 * (med["semi"] - med["plain"]),
+                            "per_round": [1e3 * x for x in diffs],
+                            "median": 1e3 * statistics.median(diffs),
+                            "min": 1e3 * min(diffs), "max": 1e3 * max(diffs)},
+           "round_spread_us": {"plain": 1e3 * (max(times["plain"]) - min(times["plain"])),
+                               "semi": 1e3 * (max(times["semi"]) - min(times["semi"]))},
+           "losses_last": [float(x) for x in steps["semi"].losses_semi.tolist()]}
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"plain_ms": med["plain"], "semi_ms": med["semi"],
+                      "semi_cost_us": out["semi_cost_us"]["median"],
+                      "round_spread_us": out["round_spread_us"], "kept_share": out["kept_share"]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join("profiles", "segadv_bench.json"))
+    ap.add_argument("--semi", action="store_true",
+                    help="time semi=True against semi=False (profiles/segadv_semi_bench.json)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join("profiles", "segadv_semi_bench.json" if a.semi else "segadv_bench.json")
     if not torch.cuda.is_available():
         sys.exit("segadv_bench: no HIP device (the steps are timed on the MI355X only)")
+    if a.semi:
+        return _semi(a)
     import adversarial_learning_on_pointclouds_amd as pc
     B, N = 16, 2048
     rng = np.random.default_rng(0)
