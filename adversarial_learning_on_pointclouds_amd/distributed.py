@@ -25,6 +25,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from .flat import capture_graphs
+
 
 def _avg_(t, group=None):
     _avg_async(t, group)()
@@ -130,21 +132,12 @@ class DataParallelAdvStep:
         else:
             g_fwd = s.capture_on(pts_gt, labels, pts_nogt, apply_adam=False)
         parts = (1, 2) if self._split() and getattr(s, "supports_split_adam", False) else (0,)
-        saved = s._snapshot()
-        side = torch.cuda.Stream(device=s.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up outside the capture
+
+        def warmup():
             for part in parts:
                 s.adam(part=part)
-        torch.cuda.current_stream().wait_stream(side)
-        g_adam = []
-        for part in parts:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                s.adam(part=part)
-            g_adam.append(g)
-        torch.cuda.synchronize()
-        s._restore(saved)
+        g_adam = capture_graphs(s.device, warmup, [lambda part=part: s.adam(part=part)
+                                                   for part in parts], s.graph_state())
         return _DPGraph(g_fwd, g_adam, s, self.group)
 
     def capture_single(self, pts_gt, labels, pts_nogt):
@@ -155,20 +148,11 @@ class DataParallelAdvStep:
         iteration instead of four graphs around host-issued collectives
         (VERDICT r05 item 6).  State is left as it was before the capture."""
         s = self.step
-        saved = s._snapshot()
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream(device=s.device)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):  # warm-up: communicators and kernels initialised
+        def body():
             self(pts_gt, labels, pts_nogt)
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self(pts_gt, labels, pts_nogt)
-        torch.cuda.synchronize()
-        s._restore(saved)
-        return g
+        # the warm-up initialises the communicators and kernels; its collectives
+        # are through before the capture begins
+        return capture_graphs(s.device, body, body, s.graph_state(), sync_before_capture=True)
 
 
 class _DPGraph:

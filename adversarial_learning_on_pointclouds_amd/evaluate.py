@@ -24,6 +24,7 @@ import torch
 from . import _lib, ops
 from ._lib import check, ptr, stream_ptr
 from .dataset import DeviceCloudLoader
+from .flat import capture_graphs
 from .metric import object_names, part_ranges
 from .pointnet import PointNetCls
 
@@ -106,21 +107,10 @@ class _Evaluator:
                                            stream_ptr()), "pcadv_iter_epilogue")
 
     def _capture(self):
-        state = [self.counters, self.acc]
-        saved = [t.clone() for t in state]
-        self.counters[0:1].zero_()  # the warm-up gathers batch 0 of whatever order is held
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):  # warm-up outside the capture
+        def warmup():
+            self.counters[0:1].zero_()  # it gathers batch 0 of whatever order is held
             self._full_batch()
-        cur.wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._full_batch()
-        torch.cuda.synchronize()
-        for dst, src in zip(state, saved):
-            dst.copy_(src)
+        g = capture_graphs(self.device, warmup, self._full_batch, [self.counters, self.acc])
         self.graph = g
         self.captures += 1
 

@@ -38,7 +38,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, stream_ptr
-from .step import _step_tensor, set_optimizer_step
+from .flat import FlatAdam
+from .step import FusedStep
 
 __all__ = ["PointNetSeg", "SegTrainStep", "SegAdvTrainStep", "seg_cross_entropy", "seg_forward",
            "seg_backward"]
@@ -560,7 +561,56 @@ class PointNetSeg(nn.Module):
         return logits.permute(0, 2, 1), g.unsqueeze(2)
 
 
-class SegTrainStep:
+class _SegStep(FusedStep):
+    """What the two PointNetSeg steps share: lr / betas / eps as attributes (the
+    discriminator's with a _D suffix), the generator's flat state (param, grad,
+    m, v, grad_views, params, step_count) with the bf16 hi / lo planes of all
+    its parameters (one split per step feeds every forward GEMM's weight
+    operand), a discriminator's flat state under its own step counter, and one
+    pcadv_adam launch per network."""
+
+    def __init__(self, model, optimizers, hyper, device, precision, keep_activations,
+                 model_D=None):
+        # the model's precision unless given ("fp32" / "bf16x3")
+        self.precision = _check_precision(precision or getattr(model, "precision", "fp32"))
+        super().__init__(device, optimizers, hyper)
+        # keep_activations: hold the last step's forward tensors in self.fw (for
+        # inspection / tests); off by default, so a step's per-point activations
+        # (hundreds of MB at B=16, N=2048) are released when it returns
+        self.keep_activations = bool(keep_activations)
+        self.fw = None
+        dev, self.model = self.device, model
+        G = FlatAdam(model, optimizers[0], dev)
+        self.param, self.grad, self.m, self.v = G.param, G.grad, G.m, G.v
+        self.grad_views, self.params, self.numel = G.grad_views, G.params, G.numel
+        self.step_count = torch.full((1,), G.t0, device=dev, dtype=torch.int32)
+        self.wph = torch.empty(G.numel, device=dev, dtype=torch.bfloat16)
+        self.wpl = torch.empty(G.numel, device=dev, dtype=torch.bfloat16)
+        self.wplanes = [(self.wph[o:o + p.numel()], self.wpl[o:o + p.numel()])
+                        for p, o in zip(G.params, G.offsets)]
+        self.nets, self.counts = (G,), (self.step_count,)
+        if model_D is not None:
+            self.model_D = model_D
+            D = FlatAdam(model_D, optimizers[1], dev)
+            self.d_param, self.d_grad, self.d_m, self.d_v = D.param, D.grad, D.m, D.v
+            self.d_grad_views, self.d_params, self.d_numel = D.grad_views, D.params, D.numel
+            self.step_count_D = torch.full((1,), D.t0, device=dev, dtype=torch.int32)
+            self.nets, self.counts = (G, D), (self.step_count, self.step_count_D)
+
+    def _store_hyper(self, k, lr, betas, eps):
+        s = "_D" if k else ""
+        setattr(self, "lr" + s, lr)
+        setattr(self, "betas" + s, betas)
+        setattr(self, "eps" + s, eps)
+
+    def _adam(self, k, lr, betas, eps):
+        f = self.nets[k]
+        check(self.lib.pcadv_adam(_p(f.param), _p(f.grad), _p(f.m), _p(f.v), f.numel,
+                                  _p(self.counts[k]), lr, betas[0], betas[1], eps, stream_ptr()),
+              "pcadv_adam")
+
+
+class SegTrainStep(_SegStep):
     """One iteration of run_training_pointnet_seg (utils/trainer.py:334-349:
     forward, CrossEntropyLoss over every point, (lambda_seg * l).backward(),
     optimizer.step() with Adam) as native launches on one stream, capturable
@@ -574,70 +624,16 @@ class SegTrainStep:
 
     def __init__(self, model, optimizer=None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  lambda_seg=1.0, device="cuda", keep_activations=False, precision=None):
-        self.lib = _lib.load()
-        # the model's precision unless given ("fp32" / "bf16x3")
-        self.precision = _check_precision(precision or getattr(model, "precision", "fp32"))
-        # keep_activations: hold the last step's forward tensors in self.fw (for
-        # inspection / tests); off by default, so a step's per-point activations
-        # (hundreds of MB at B=16, N=2048) are released when it returns
-        self.keep_activations = bool(keep_activations)
-        self.fw = None
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("SegTrainStep runs on the HIP device only")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device, self.model = dev, model
-        if optimizer is not None:
-            g = optimizer.param_groups[0]
-            lr, betas, eps = g["lr"], tuple(g["betas"]), g["eps"]
-        self.lr, self.betas, self.eps, self.lambda_seg = float(lr), betas, float(eps), float(lambda_seg)
-        named = list(model.named_parameters())
-        offs, n = [], 0
-        for _, p in named:
-            offs.append(n)
-            n += (p.numel() + 63) // 64 * 64  # 256-B aligned views
-        self.numel = n
-        self.param = torch.zeros(n, device=dev)
-        self.grad = torch.zeros(n, device=dev)
-        self.m = torch.zeros(n, device=dev)
-        self.v = torch.zeros(n, device=dev)
-        self.grad_views = []
-        t0 = 0
-        for (name, p), o in zip(named, offs):
-            k = p.numel()
-            self.param[o:o + k].copy_(p.detach().reshape(-1))
-            st = optimizer.state.get(p) if optimizer is not None else None
-            if st and "exp_avg" in st:  # Adam state the optimizer already holds carries over
-                self.m[o:o + k].copy_(st["exp_avg"].detach().reshape(-1))
-                self.v[o:o + k].copy_(st["exp_avg_sq"].detach().reshape(-1))
-                t0 = max(t0, int(float(st.get("step", 0))))
-            p.data = self.param[o:o + k].view_as(p)
-            gv = self.grad[o:o + k].view_as(p)
-            p.grad = gv
-            self.grad_views.append(gv)
-        if optimizer is not None:
-            for (name, p), o in zip(named, offs):
-                k = p.numel()
-                optimizer.state[p] = {"step": _step_tensor(optimizer, p, t0),
-                                      "exp_avg": self.m[o:o + k].view_as(p),
-                                      "exp_avg_sq": self.v[o:o + k].view_as(p)}
-        self.step_count = torch.full((1,), t0, device=dev, dtype=torch.int32)
-        self.params = [p for _, p in named]
-        # bf16 hi / lo planes of all parameters: one split per step feeds every
-        # forward GEMM's weight operand
-        self.wph = torch.empty(n, device=dev, dtype=torch.bfloat16)
-        self.wpl = torch.empty(n, device=dev, dtype=torch.bfloat16)
-        self.wplanes = [(self.wph[o:o + p.numel()], self.wpl[o:o + p.numel()])
-                        for (_, p), o in zip(named, offs)]
+        super().__init__(model, (optimizer,), [(lr, betas, eps)], device, precision,
+                         keep_activations)
+        self.lambda_seg = float(lambda_seg)
         # fp32 mode: the three-way split (hi, mid = wph, wpl, and lo), one launch
         # per step, for the forward GEMMs' weight operands
-        self.wpl3 = torch.empty(n, device=dev, dtype=torch.bfloat16) if _B3 else None
-        self.wplanes3 = ([(self.wph[o:o + p.numel()], self.wpl[o:o + p.numel()],
-                           self.wpl3[o:o + p.numel()]) for (_, p), o in zip(named, offs)]
+        self.wpl3 = torch.empty_like(self.wph) if _B3 else None
+        self.wplanes3 = ([(hi, mid, self.wpl3[o:o + hi.numel()])
+                          for (hi, mid), o in zip(self.wplanes, self.nets[0].offsets)]
                          if _B3 else None)
-        self.optimizer = optimizer
-        self.loss = torch.zeros((), device=dev)
+        self.loss = torch.zeros((), device=self.device)
         self.graph = None
 
     def __call__(self, pts, cls, seg, apply_adam=True):
@@ -668,90 +664,22 @@ class SegTrainStep:
         return self.loss
 
     def adam(self):
-        check(self.lib.pcadv_adam(_p(self.param), _p(self.grad), _p(self.m), _p(self.v), self.numel,
-                                  _p(self.step_count), self.lr, self.betas[0], self.betas[1],
-                                  self.eps, stream_ptr()), "pcadv_adam")
+        self._adam(0, self.lr, self.betas, self.eps)
 
     def capture_on(self, pts, cls, seg):
         """A HIP graph of one step reading the given resident buffers (state is
         restored to what it was before the warm-up)."""
-        saved = [t.clone() for t in (self.param, self.m, self.v, self.step_count)]
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        def body():
             self(pts, cls, seg)
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self(pts, cls, seg)
-        torch.cuda.synchronize()
-        for dst, src in zip((self.param, self.m, self.v, self.step_count), saved):
-            dst.copy_(src)
-        return g
+        return self._capture(body, body)
 
     @property
     def losses(self):
         """The loss as a 1-vector (the trainers' loss-ring interface)."""
         return self.loss.view(1)
 
-    def graph_state(self):
-        """What a captured iteration's warm-up changes (restored after it)."""
-        return [self.param, self.m, self.v, self.step_count]
 
-    def sync_hyper(self):
-        """lr / betas / eps as the optimizer holds them now (a graph captured
-        before keeps the old values: the trainer recaptures on a change)."""
-        if self.optimizer is not None:
-            g = self.optimizer.param_groups[0]
-            self.lr, self.betas, self.eps = float(g["lr"]), tuple(float(b) for b in g["betas"]), \
-                float(g["eps"])
-
-    def sync_optimizer_state(self):
-        if self.optimizer is not None:
-            set_optimizer_step(self.optimizer, float(self.step_count.item()))
-
-
-def _flat_state(model, optimizer, dev):
-    """The model's parameters as views of one flat f32 buffer, their .grad views
-    of one flat gradient buffer, and flat Adam moments handed to `optimizer` as
-    its state (what SegTrainStep does for the generator).  Returns (param, grad,
-    m, v, grad_views, t0, numel, offsets)."""
-    named = list(model.named_parameters())
-    offs, n = [], 0
-    for _, p in named:
-        offs.append(n)
-        n += (p.numel() + 63) // 64 * 64  # 256-B aligned views
-    param, grad = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-    m, v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-    views, t0 = [], 0
-    for (_, p), o in zip(named, offs):
-        k = p.numel()
-        param[o:o + k].copy_(p.detach().reshape(-1))
-        st = optimizer.state.get(p) if optimizer is not None else None
-        if st and "exp_avg" in st:  # Adam state the optimizer already holds carries over
-            m[o:o + k].copy_(st["exp_avg"].detach().reshape(-1))
-            v[o:o + k].copy_(st["exp_avg_sq"].detach().reshape(-1))
-            t0 = max(t0, int(float(st.get("step", 0))))
-        p.data = param[o:o + k].view_as(p)
-        p.grad = grad[o:o + k].view_as(p)
-        views.append(p.grad)
-    if optimizer is not None:
-        for (_, p), o in zip(named, offs):
-            k = p.numel()
-            optimizer.state[p] = {"step": _step_tensor(optimizer, p, t0),
-                                  "exp_avg": m[o:o + k].view_as(p),
-                                  "exp_avg_sq": v[o:o + k].view_as(p)}
-    return param, grad, m, v, views, t0, n, offs
-
-
-def _adam_hyper(optimizer, lr, betas, eps):
-    if optimizer is not None:
-        g = optimizer.param_groups[0]
-        return float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"])
-    return float(lr), tuple(betas), float(eps)
-
-
-class SegAdvTrainStep:
+class SegAdvTrainStep(_SegStep):
     """One iteration of run_training_seg (utils/trainer.py:873-966) with
     ImagePool(0), PointNetSeg + PointwiseDiscNet and two Adams, as native
     launches on one stream, capturable into a HIP graph:
@@ -785,42 +713,19 @@ class SegAdvTrainStep:
                  lambda_adv=0.01, lr=1e-4, lr_D=1e-4, betas=(0.9, 0.999), eps=1e-8, device="cuda",
                  precision=None, seed=0, keep_activations=False, lambda_semi=1.0, semi_th=0.8):
         from .discriminator import PointwiseDiscNet
-        self.lib = _lib.load()
         if not isinstance(model, PointNetSeg) or not isinstance(model_D, PointwiseDiscNet):
             raise TypeError("SegAdvTrainStep: expected a PointNetSeg and a PointwiseDiscNet")
         if model_D.input_dim != model.output_dim:
             raise ValueError(f"model_D takes {model_D.input_dim} channels, the generator predicts "
                              f"{model.output_dim} classes")
-        self.precision = _check_precision(precision or getattr(model, "precision", "fp32"))
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("SegAdvTrainStep runs on the HIP device only")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device, self.model, self.model_D = dev, model, model_D
-        self.optimizer, self.optimizer_D = optimizer, optimizer_D
+        super().__init__(model, (optimizer, optimizer_D), [(lr, betas, eps), (lr_D, betas, eps)],
+                         device, precision, keep_activations, model_D)
         self.lambda_seg, self.lambda_adv, self.seed = float(lambda_seg), float(lambda_adv), int(seed)
         self.lambda_semi, self.semi_th = float(lambda_semi), float(semi_th)
-        self.lr, self.betas, self.eps = _adam_hyper(optimizer, lr, betas, eps)
-        self.lr_D, self.betas_D, self.eps_D = _adam_hyper(optimizer_D, lr_D, betas, eps)
-        (self.param, self.grad, self.m, self.v, self.grad_views, t0, self.numel,
-         offs) = _flat_state(model, optimizer, dev)
-        (self.d_param, self.d_grad, self.d_m, self.d_v, self.d_grad_views, t0d, self.d_numel,
-         _) = _flat_state(model_D, optimizer_D, dev)
-        self.step_count = torch.full((1,), t0, device=dev, dtype=torch.int32)
-        self.step_count_D = torch.full((1,), t0d, device=dev, dtype=torch.int32)
-        self.params = [p for _, p in model.named_parameters()]
-        self.d_params = [p for _, p in model_D.named_parameters()]
-        n = self.numel
-        self.wph = torch.empty(n, device=dev, dtype=torch.bfloat16)
-        self.wpl = torch.empty(n, device=dev, dtype=torch.bfloat16)
-        self.wplanes = [(self.wph[o:o + p.numel()], self.wpl[o:o + p.numel()])
-                        for p, o in zip(self.params, offs)]
         # [loss_seg, loss_adv, loss_D, loss_D's GT part, its no-GT part, loss_semi]
-        self.loss_buf = torch.zeros(6, device=dev)
-        self.kept_buf = torch.zeros(1, device=dev, dtype=torch.int32)
-        self.keep_activations = bool(keep_activations)
-        self.fw = self.d_out = self.semi_labels = None
+        self.loss_buf = torch.zeros(6, device=self.device)
+        self.kept_buf = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self.d_out = self.semi_labels = None
         self._ws = None
         self._semi_stale = False
 
@@ -896,12 +801,8 @@ class SegAdvTrainStep:
 
     def adam(self):
         """optimizer.step() and optimizer_D.step() (trainer.py:965-966)."""
-        check(self.lib.pcadv_adam(_p(self.param), _p(self.grad), _p(self.m), _p(self.v), self.numel,
-                                  _p(self.step_count), self.lr, self.betas[0], self.betas[1],
-                                  self.eps, stream_ptr()), "pcadv_adam")
-        check(self.lib.pcadv_adam(_p(self.d_param), _p(self.d_grad), _p(self.d_m), _p(self.d_v),
-                                  self.d_numel, _p(self.step_count_D), self.lr_D, self.betas_D[0],
-                                  self.betas_D[1], self.eps_D, stream_ptr()), "pcadv_adam")
+        self._adam(0, self.lr, self.betas, self.eps)
+        self._adam(1, self.lr_D, self.betas_D, self.eps_D)
 
     @property
     def losses(self):
@@ -920,52 +821,11 @@ class SegAdvTrainStep:
         int32; 0 for a step without the term)."""
         return self.kept_buf[0]
 
-    def graph_state(self):
-        """What a captured iteration's warm-up changes (restored after it)."""
-        return [self.param, self.m, self.v, self.step_count, self.d_param, self.d_m, self.d_v,
-                self.step_count_D]
-
     def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
                    semi=False):
         """One HIP graph of a step reading the given resident buffers: a single
         stream, no parallel branches (state is restored to what it was before
         the warm-up).  `semi` is baked into the graph."""
-        saved = [t.clone() for t in self.graph_state()]
-        args = (pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True, semi)
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self(*args)
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self(*args)
-        torch.cuda.synchronize()
-        for dst, src in zip(self.graph_state(), saved):
-            dst.copy_(src)
-        return g
-
-    def sync_hyper(self):
-        """lr / betas / eps as the optimizers hold them now (a graph captured
-        before keeps the old values)."""
-        self.lr, self.betas, self.eps = _adam_hyper(self.optimizer, self.lr, self.betas, self.eps)
-        self.lr_D, self.betas_D, self.eps_D = _adam_hyper(self.optimizer_D, self.lr_D, self.betas_D,
-                                                          self.eps_D)
-
-    def sync_optimizer_state(self):
-        if self.optimizer is not None:
-            set_optimizer_step(self.optimizer, float(self.step_count.item()))
-        if self.optimizer_D is not None:
-            set_optimizer_step(self.optimizer_D, float(self.step_count_D.item()))
-
-    def after_eager(self):
-        """After iterations run by the torch optimizers on the same (flat)
-        parameters and moments: take over their step counts and hand the
-        modules' .grad back to the flat gradient buffers."""
-        for opt, cnt in ((self.optimizer, self.step_count), (self.optimizer_D, self.step_count_D)):
-            steps = [int(float(st["step"])) for st in opt.state.values() if st] if opt else []
-            if steps:
-                cnt.fill_(max(steps))
-        for ps, views in ((self.params, self.grad_views), (self.d_params, self.d_grad_views)):
-            for p, gv in zip(ps, views):
-                p.grad = gv
+        def body():
+            self(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True, semi)
+        return self._capture(body, body)

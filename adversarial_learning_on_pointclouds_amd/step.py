@@ -8,6 +8,10 @@ memory.  Both networks' gradients share ONE flat buffer (generator first), so a
 data-parallel run averages them with a single all-reduce.  Adam moments are
 flat too and are handed to a torch Adam optimizer's state as views
 (exp_avg / exp_avg_sq), so optimizer.state_dict() stays meaningful.
+
+FusedStep is the base of every step object (these four and seg.py's two): what
+the trainers call on a step, each network's flat.FlatAdam, graph capture
+through flat.capture_graphs.
 """
 from __future__ import annotations
 
@@ -19,30 +23,17 @@ import torch
 
 from . import _lib
 from ._lib import AdvArgs, D_LAYOUT, D_NUMEL, G_LAYOUT, G_NUMEL, check, stream_ptr
+from .flat import (FlatAdam, adam_hyper, capture_graphs, pad64, sequential_layout,
+                   set_optimizer_step)
 
-D_GRAD_OFFSET = (G_NUMEL + 63) // 64 * 64  # D grads start 256-B aligned
+D_GRAD_OFFSET = pad64(G_NUMEL)  # D grads start 256-B aligned
 G_LATE_END = G_LAYOUT["fc1.weight"]  # grad_flat[:G_LATE_END]: the feature backward's (part 2)
 
 
 def flatten_params(module, layout, numel, device):
-    """Copy a module's parameters into one flat buffer and rebind them as views."""
-    flat = torch.zeros(numel, device=device, dtype=torch.float32)
-    named = dict(module.named_parameters())
-    if set(named) != set(layout):
-        raise ValueError(f"{type(module).__name__}: parameters {sorted(set(named) ^ set(layout))} "
-                         "do not match the fused-step layout")
-    for name, off in layout.items():
-        p = named[name]
-        n = p.numel()
-        flat[off:off + n].copy_(p.detach().reshape(-1))
-        p.data = flat[off:off + n].view_as(p)
-    return flat
-
-
-def _views(flat, module, layout):
-    named = dict(module.named_parameters())
-    return {name: flat[off:off + named[name].numel()].view_as(named[name])
-            for name, off in layout.items()}
+    """Copy a module's parameters into one flat buffer and rebind them as views
+    (FlatAdam without an optimizer; its .grad views come with it)."""
+    return FlatAdam(module, None, device, layout, numel).param
 
 
 def _precision(name):
@@ -57,63 +48,6 @@ def _precision(name):
 # (pcadv_pw_chain, bitwise the per-layer pcadv_pw_fwd launches); PCADV_FT_CHAIN=0
 # keeps the six per-layer launches (A/B)
 _FT_CHAIN = os.environ.get("PCADV_FT_CHAIN", "1") == "1"
-
-
-def _align(nbytes):
-    return (nbytes + 255) // 256 * 256
-
-
-def _adopt_adam_state(optimizer, module, m_flat, v_flat, layout):
-    """Seed flat Adam moments from state an optimizer already holds (a
-    load_state_dict before the first iteration, or the views of a previous
-    step object the trainer rebuilt): exp_avg / exp_avg_sq are copied in and
-    the largest 'step' is returned (0 when there is none)."""
-    if optimizer is None:
-        return 0
-    steps = 0
-    named = dict(module.named_parameters())
-    for name, off in layout.items():
-        st = optimizer.state.get(named[name])
-        if not st or "exp_avg" not in st:
-            continue
-        n = named[name].numel()
-        m_flat[off:off + n].copy_(st["exp_avg"].detach().reshape(-1))
-        v_flat[off:off + n].copy_(st["exp_avg_sq"].detach().reshape(-1))
-        steps = max(steps, int(float(st.get("step", 0))))
-    return steps
-
-
-def _step_tensor(optimizer, p, t):
-    """'step' as torch.optim.Adam keeps it for p: an f32 scalar on p's device
-    when its group is capturable or fused (the step then runs on the device,
-    and Adam refuses a CPU count), a CPU f32 scalar otherwise."""
-    for g in optimizer.param_groups:
-        if any(q is p for q in g["params"]):
-            if g.get("capturable", False) or g.get("fused", False):
-                return torch.tensor(float(t), dtype=torch.float32, device=p.device)
-            break
-    return torch.tensor(float(t), dtype=torch.float32)
-
-
-def set_optimizer_step(optimizer, t):
-    """Every state entry's 'step' = t (the device step counter's value)."""
-    if optimizer is None:
-        return
-    for p, st in optimizer.state.items():
-        if st:
-            st["step"] = _step_tensor(optimizer, p, t)
-
-
-def _bind_adam_state(optimizer, module, m_flat, v_flat, grad_flat, layout, step_t):
-    """p.grad and the optimizer's exp_avg / exp_avg_sq become views of the flat
-    buffers; 'step' holds the completed-step count."""
-    mv, vv, gv = _views(m_flat, module, layout), _views(v_flat, module, layout), \
-        _views(grad_flat, module, layout)
-    for name, p in module.named_parameters():
-        p.grad = gv[name]
-        if optimizer is not None:
-            optimizer.state[p] = {"step": _step_tensor(optimizer, p, step_t),
-                                  "exp_avg": mv[name], "exp_avg_sq": vv[name]}
 
 
 def _fill_epilogue(a, epi, gather=None):
@@ -131,26 +65,176 @@ def _fill_epilogue(a, epi, gather=None):
         a.epi_ring_count = ring.count.data_ptr()
 
 
-class AdvTrainStep:
-    """run_training's iteration body for PointNetCls(k=40) + DeepConvDiscNet(40, 1).
+class FusedStep:
+    """What the trainers rely on in every fused step object:
+    graph_state(), after_capture(), sync_hyper(), sync_optimizer_state(),
+    folds_iteration (with folded_gather / folded_epilogue when true), and
+    after_torch_step() / after_eager() once torch optimizers ran an iteration
+    on the same flat state.
 
-    Call with device tensors pts_gt (B, N, 3) f32, labels (B,) int64, pts_nogt
-    (B, N, 3) f32.  Dropout masks and soft D labels are drawn on device from
-    Philox keyed by (seed, step) unless given explicitly (parity mode:
-    masks=(gt, nogt) each (B, 256) {0,1}; soft=(gt, nogt) each (B,)).
-    Returns the device tensor [loss_cls, loss_adv, loss_D_gt, loss_D_nogt,
-    loss_semi, semi_ratio] (no host sync: read it when you log,
-    trainer.py:561-572).  semi=True adds run_training_semi's pseudo-label term
-    (utils/trainer.py:716-743: lambda_semi x CrossEntropyLoss(ignore_index=255)
-    of the no-GT logits against their argmax, clouds with D <= semi_th ignored).
-    rng_rank / rng_world: this step is rank rng_rank of a data-parallel job of
-    rng_world ranks, each holding the rows [rank B, rank B + B) of the global
-    GT and no-GT batches: the device-drawn masks and labels are those of the
-    one-process step on the global batch (pcadv_adv_args.rng_rank, ABI 6).
-    """
+    A subclass passes its optimizers (one per network, None allowed) and the
+    (lr, betas, eps) each network takes without one, implements _store_hyper,
+    and sets self.nets (its FlatAdam objects) and self.counts (the device step
+    counter of each; one tensor may serve two networks)."""
 
+    # one (betas, eps) pair serves both networks' Adam (only the lrs differ)
+    shared_adam_pair = False
+    # the step takes the iteration's gathers and epilogue into its own launches
+    folds_iteration = False
+
+    def __init__(self, device, optimizers, hyper):
+        self.lib = _lib.load()
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError(f"{type(self).__name__} runs on the HIP device only")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.optimizers = tuple(optimizers)
+        for k, (lr, betas, eps) in enumerate(hyper):
+            self._store_hyper(k, float(lr), tuple(float(b) for b in betas), float(eps))
+        self.sync_hyper()
+
+    def _store_hyper(self, k, lr, betas, eps):
+        """Network k's Adam hyperparameters, where the step's launches read them
+        (betas / eps None: network k shares network 0's)."""
+        raise NotImplementedError
+
+    def sync_hyper(self):
+        """Re-read lr / betas / eps from the optimizers (a scheduler may have
+        changed them); a graph captured before keeps the old values, so the
+        trainer recaptures when they change."""
+        first = None
+        for k, opt in enumerate(self.optimizers):
+            if opt is None:
+                continue
+            lr, betas, eps = adam_hyper(opt)
+            if k and self.shared_adam_pair:
+                gd = opt.param_groups[0]
+                if first is not None and ((betas, eps) != first
+                                          or float(gd.get("weight_decay", 0) or 0) != 0.0):
+                    raise ValueError(
+                        "the fused adversarial step applies the generator optimizer's betas / eps "
+                        "to the discriminator too: optimizer_D now has betas "
+                        f"{tuple(gd['betas'])}, eps {gd['eps']}, weight_decay "
+                        f"{gd.get('weight_decay', 0)} against {first[0]}, {first[1]}, 0")
+                betas = eps = None
+            elif k == 0:
+                first = (betas, eps)
+            self._store_hyper(k, lr, betas, eps)
+
+    def sync_optimizer_state(self):
+        """Copy the device step counters into the torch optimizers' 'step'."""
+        t = {id(c): float(c.item()) for c in self.counts}
+        for f, c in zip(self.nets, self.counts):
+            set_optimizer_step(f.optimizer, t[id(c)])
+
+    def graph_state(self):
+        """What a captured iteration's warm-up changes (restored after it)."""
+        return ([t for f in self.nets for t in (f.param, f.m, f.v)]
+                + list({id(c): c for c in self.counts}.values()))
+
+    def after_capture(self):
+        pass
+
+    def _capture(self, warmup, body):
+        """A HIP graph of body() after warmup(); state left as it was."""
+        return capture_graphs(self.device, warmup, body, self.graph_state())
+
+    def after_torch_step(self):
+        """After an iteration the trainer ran through autograd and the torch
+        optimizers (unequal GT / no-GT batches): the device step counter
+        advances with torch's, and each p.grad (a fresh tensor after
+        zero_grad + backward) is copied back into the flat gradient buffer
+        and rebound as its view."""
+        for c in {id(c): c for c in self.counts}.values():
+            c += 1
+        for f in self.nets:
+            for p, gv in zip(f.params, f.grad_views):
+                if p.grad is None:
+                    gv.zero_()  # no gradient this iteration: not the last fused one's
+                elif p.grad.data_ptr() != gv.data_ptr():
+                    gv.copy_(p.grad)
+                p.grad = gv
+
+    def after_eager(self):
+        """After iterations run by the torch optimizers on the same (flat)
+        parameters and moments: take over their step counts and hand the
+        modules' .grad back to the flat gradient buffers."""
+        for f, cnt in zip(self.nets, self.counts):
+            opt = f.optimizer
+            steps = [int(float(st["step"])) for st in opt.state.values() if st] if opt else []
+            if steps:
+                cnt.fill_(max(steps))
+            for p, gv in zip(f.params, f.grad_views):
+                p.grad = gv
+
+
+class _ModelNetStep(FusedStep):
+    """The PointNetCls steps' common part (pcadv_adv_args): the hp dict, the
+    generator's (and discriminator's) flat state under one step counter, both
+    gradients in one grad_flat (generator first, D at the next 64-float
+    boundary: data parallelism all-reduces that one buffer), the losses /
+    logits / workspace buffers, the draws' seed and rank, and the iteration's
+    gathers and epilogue folded into the step's launches."""
+
+    folds_iteration = True
     _epilogue = None  # (counters, ncounters, _LossRing) folded into the last launch
     _gather = None    # ctypes GatherJob array gathered by the first launch
+
+    def __init__(self, model, model_D, B, N, optimizers, lrs, betas, eps, hp, nlosses, seed,
+                 device, rng_rank, rng_world):
+        g_layout, g_numel = self._layout(model, N)
+        self.hp = dict(hp, p=float(model.dropout.p))
+        super().__init__(device, optimizers, [(lr, betas, eps) for lr in lrs])
+        self.set_rng_rank(rng_rank, rng_world)
+        self.model, self.B, self.N = model, int(B), int(N)
+        dev = self.device
+        if model_D is None:
+            G = FlatAdam(model, optimizers[0], dev, g_layout, g_numel)
+            nets = (G,)
+        else:
+            self.model_D = model_D
+            d_off = pad64(g_numel)
+            self.grad_flat = torch.zeros(d_off + D_NUMEL, device=dev)
+            G = FlatAdam(model, optimizers[0], dev, g_layout, g_numel,
+                         grad=self.grad_flat[:g_numel])
+            D = FlatAdam(model_D, optimizers[1], dev, D_LAYOUT, D_NUMEL,
+                         grad=self.grad_flat[d_off:])
+            nets = (G, D)
+            self.d_param, self.d_grad, self.d_m, self.d_v = D.param, D.grad, D.m, D.v
+        self.g_param, self.g_grad, self.g_m, self.g_v = G.param, G.grad, G.m, G.v
+        # Adam state the optimizers already hold carries over (one step count
+        # serves both networks: run_training steps them together)
+        t0 = max(f.t0 for f in nets)
+        for f in nets:
+            if f.t0 != t0:
+                f.bind(t0)
+        self.step_count = torch.full((1,), t0, device=dev, dtype=torch.int32)
+        self.nets, self.counts = nets, (self.step_count,) * len(nets)
+        self.losses = torch.zeros(nlosses, device=dev)
+        self.logits = torch.zeros(len(nets) * self.B, 40, device=dev)
+        nbytes = self.lib.pcadv_adv_step_workspace_bytes(self.B, self.N)
+        self.workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._keep = []
+
+    def _layout(self, model, N):
+        """(layout, numel) of the generator's flat buffers."""
+        return G_LAYOUT, G_NUMEL
+
+    def _store_hyper(self, k, lr, betas, eps):
+        if k == 0:
+            self.hp.update(lr=lr, betas=betas, eps=eps)
+        else:
+            self.hp["lr_D"] = lr
+
+    def set_rng_rank(self, rank, world):
+        """Key the device draws by the global batch's rows (data parallelism)."""
+        rank, world = int(rank), int(world)
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"rng rank {rank} of {world}")
+        self.rng_rank, self.rng_world = rank, world
 
     @contextlib.contextmanager
     def folded_epilogue(self, counters=None, ncounters=0, ring=None):
@@ -176,56 +260,107 @@ class AdvTrainStep:
         finally:
             self._gather = None
 
+    # the feature-transform steps run the folded gathers / epilogue as their
+    # call's own first and last launches
+    def _pre(self):
+        if self._gather is not None:
+            check(self.lib.pcadv_gather_clouds_multi(self._gather, len(self._gather),
+                                                     stream_ptr()), "pcadv_gather_clouds_multi")
+
+    def _post(self):
+        if self._epilogue is None:
+            return
+        counters, n, ring = self._epilogue
+        P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        if ring is None:
+            check(self.lib.pcadv_iter_epilogue(P(counters), n, None, 0, None, 0, None,
+                                               stream_ptr()), "pcadv_iter_epilogue")
+        else:
+            check(self.lib.pcadv_iter_epilogue(P(counters), n, P(self.losses), ring.nl,
+                                               P(ring.ring), ring.slots, P(ring.count),
+                                               stream_ptr()), "pcadv_iter_epilogue")
+
+    def _fill_state(self, a):
+        """pcadv_adv_args' flat state, step counter and Adam hyperparameters."""
+        a.g_param, a.g_grad = self.g_param.data_ptr(), self.g_grad.data_ptr()
+        a.g_m, a.g_v = self.g_m.data_ptr(), self.g_v.data_ptr()
+        hp = self.hp
+        if len(self.nets) == 2:
+            a.d_param, a.d_grad = self.d_param.data_ptr(), self.d_grad.data_ptr()
+            a.d_m, a.d_v = self.d_m.data_ptr(), self.d_v.data_ptr()
+            a.lr_d = hp["lr_D"]
+        a.step_count = self.step_count.data_ptr()
+        a.lr_g, a.beta1, a.beta2, a.eps = hp["lr"], hp["betas"][0], hp["betas"][1], hp["eps"]
+
+    def _capture_launches(self, warmup, entry, what, args):
+        """One HIP graph of entry(a) for each prepared pcadv_adv_args in `args`
+        (kept alive with the step) after warmup(); state left as it was."""
+        self._keep.extend(args)
+
+        def body():
+            for a in args:
+                check(entry(ctypes.byref(a), stream_ptr()), what)
+        return self._capture(warmup, body)
+
+
+class _FtExtractor:
+    """The feature-transform steps' part: ft_layout, N a multiple of 128, the
+    parameters and flat gradient views by name for _ft_extractor_forward /
+    _ft_extractor_backward, and one iteration per graph."""
+
+    def _layout(self, model, N):
+        if not getattr(model, "feature_transform", False):
+            raise ValueError(f"{type(self).__name__}: {self._no_ft}")
+        if int(N) % 128:
+            # the per-cloud transform x2 T and its dT = x2^T dx2t run on 64- / 128-row
+            # tiles (pcadv_pw_fwd rows_per_w, pcadv_pw_bwd_weight rows_per_group)
+            raise ValueError(f"{type(self).__name__}: N = {int(N)} points, a multiple of 128 is "
+                             "required")
+        return ft_layout(model)
+
+    def _init_ft(self, clouds):
+        G = self.nets[0]
+        self.layout, self.g_numel = G.layout, G.numel
+        self.dgmax = torch.empty(clouds, 1024, device=self.device)
+        self._p = dict(zip(G.names, G.params))
+        self._g = G.views(G.grad)
+
+    def capture_seq(self, batches, apply_adam=True):
+        raise NotImplementedError(f"{type(self).__name__}: one iteration per graph")
+
+
+class AdvTrainStep(_ModelNetStep):
+    """run_training's iteration body for PointNetCls(k=40) + DeepConvDiscNet(40, 1).
+
+    Call with device tensors pts_gt (B, N, 3) f32, labels (B,) int64, pts_nogt
+    (B, N, 3) f32.  Dropout masks and soft D labels are drawn on device from
+    Philox keyed by (seed, step) unless given explicitly (parity mode:
+    masks=(gt, nogt) each (B, 256) {0,1}; soft=(gt, nogt) each (B,)).
+    Returns the device tensor [loss_cls, loss_adv, loss_D_gt, loss_D_nogt,
+    loss_semi, semi_ratio] (no host sync: read it when you log,
+    trainer.py:561-572).  semi=True adds run_training_semi's pseudo-label term
+    (utils/trainer.py:716-743: lambda_semi x CrossEntropyLoss(ignore_index=255)
+    of the no-GT logits against their argmax, clouds with D <= semi_th ignored).
+    rng_rank / rng_world: this step is rank rng_rank of a data-parallel job of
+    rng_world ranks, each holding the rows [rank B, rank B + B) of the global
+    GT and no-GT batches: the device-drawn masks and labels are those of the
+    one-process step on the global batch (pcadv_adv_args.rng_rank, ABI 6).
+    An optimizer_D whose betas, eps or weight_decay differ from the
+    generator's is refused (ValueError): one pair serves both Adams.
+    """
+
+    shared_adam_pair = True
+
     def __init__(self, model, model_D, B, N, optimizer=None, optimizer_D=None, lr=1e-4,
                  lr_D=1e-4, betas=(0.9, 0.999), eps=1e-8, lambda_cls=1.0, lambda_adv=0.001,
                  seed=0, device="cuda", lambda_semi=1.0, semi_th=0.8, precision="fp32",
                  rng_rank=0, rng_world=1):
-        self.lib = _lib.load()
-        self.set_rng_rank(rng_rank, rng_world)
-        self.model, self.model_D = model, model_D
         self.precision = _precision(precision)
-        self.B, self.N = int(B), int(N)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("AdvTrainStep runs on the HIP device only")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        if optimizer is not None:
-            g = optimizer.param_groups[0]
-            lr, betas, eps = g["lr"], tuple(g["betas"]), g["eps"]
-        if optimizer_D is not None:
-            lr_D = optimizer_D.param_groups[0]["lr"]
-        self.hp = dict(lr=float(lr), lr_D=float(lr_D), betas=betas, eps=float(eps),
-                       lambda_cls=float(lambda_cls), lambda_adv=float(lambda_adv),
-                       p=float(model.dropout.p), lambda_semi=float(lambda_semi),
-                       semi_th=float(semi_th))
-        self.g_param = flatten_params(model, G_LAYOUT, G_NUMEL, dev)
-        self.d_param = flatten_params(model_D, D_LAYOUT, D_NUMEL, dev)
-        self.grad_flat = torch.zeros(D_GRAD_OFFSET + D_NUMEL, device=dev)
-        self.g_grad = self.grad_flat[:G_NUMEL]
-        self.d_grad = self.grad_flat[D_GRAD_OFFSET:]
-        self.g_m = torch.zeros_like(self.g_param)
-        self.g_v = torch.zeros_like(self.g_param)
-        self.d_m = torch.zeros_like(self.d_param)
-        self.d_v = torch.zeros_like(self.d_param)
-        # Adam state the optimizers already hold carries over (one step count
-        # serves both networks: run_training steps them together)
-        t0 = max(_adopt_adam_state(optimizer, model, self.g_m, self.g_v, G_LAYOUT),
-                 _adopt_adam_state(optimizer_D, model_D, self.d_m, self.d_v, D_LAYOUT))
-        self.step_count = torch.full((1,), t0, device=dev, dtype=torch.int32)
-        self._bind = ((optimizer, model, self.g_m, self.g_v, self.g_grad, G_LAYOUT),
-                      (optimizer_D, model_D, self.d_m, self.d_v, self.d_grad, D_LAYOUT))
-        for args_ in self._bind:
-            _bind_adam_state(*args_, t0)
-        self.optimizers = (optimizer, optimizer_D)
-        self.losses = torch.zeros(6, device=dev)
-        self.logits = torch.zeros(2 * self.B, 40, device=dev)
-        nbytes = self.lib.pcadv_adv_step_workspace_bytes(self.B, self.N)
-        self.workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        hp = dict(lambda_cls=float(lambda_cls), lambda_adv=float(lambda_adv),
+                  lambda_semi=float(lambda_semi), semi_th=float(semi_th))
+        super().__init__(model, model_D, B, N, (optimizer, optimizer_D), (lr, lr_D), betas, eps,
+                         hp, 6, seed, device, rng_rank, rng_world)
         self.graph = None
-        self._keep = []
 
     # ------------------------------------------------------------------
     def _args(self, pts_gt, labels, pts_nogt, masks, soft, apply_adam, semi=False, part=0):
@@ -252,14 +387,8 @@ class AdvTrainStep:
                 if s.numel() != B or s.dtype != torch.float32 or not s.is_contiguous():
                     raise ValueError("soft labels must be contiguous float32 with B elements")
             a.soft_gt, a.soft_nogt = soft[0].data_ptr(), soft[1].data_ptr()
-        a.g_param, a.g_grad = self.g_param.data_ptr(), self.g_grad.data_ptr()
-        a.g_m, a.g_v = self.g_m.data_ptr(), self.g_v.data_ptr()
-        a.d_param, a.d_grad = self.d_param.data_ptr(), self.d_grad.data_ptr()
-        a.d_m, a.d_v = self.d_m.data_ptr(), self.d_v.data_ptr()
-        a.step_count = self.step_count.data_ptr()
+        self._fill_state(a)
         hp = self.hp
-        a.lr_g, a.lr_d = hp["lr"], hp["lr_D"]
-        a.beta1, a.beta2, a.eps = hp["betas"][0], hp["betas"][1], hp["eps"]
         a.lambda_cls, a.lambda_adv, a.drop_p = hp["lambda_cls"], hp["lambda_adv"], hp["p"]
         a.rng_seed = self.seed
         a.apply_adam = int(bool(apply_adam))
@@ -275,36 +404,6 @@ class AdvTrainStep:
         _fill_epilogue(a, self._epilogue if part != 1 else None,
                        self._gather if part != 2 else None)
         return a
-
-    def sync_hyper(self):
-        """Re-read lr / betas / eps from the optimizers (a scheduler may have
-        changed them); a graph captured before keeps the old values, so the
-        trainer recaptures when they change."""
-        opt, opt_d = (self.optimizers + (None,))[:2] if hasattr(self, "optimizers") else \
-            (self.optimizer, None)
-        if opt is not None:
-            g = opt.param_groups[0]
-            self.hp.update(lr=float(g["lr"]), betas=tuple(float(b) for b in g["betas"]),
-                           eps=float(g["eps"]))
-        if opt_d is not None:
-            gd = opt_d.param_groups[0]
-            if opt is not None and (tuple(float(b) for b in gd["betas"]) != self.hp["betas"]
-                                    or float(gd["eps"]) != self.hp["eps"]
-                                    or float(gd.get("weight_decay", 0) or 0) != 0.0):
-                # the fused Adam applies ONE (betas, eps) pair to G and D (pcadv_adv_args)
-                raise ValueError(
-                    "the fused adversarial step applies the generator optimizer's betas / eps to "
-                    "the discriminator too: optimizer_D now has betas "
-                    f"{tuple(gd['betas'])}, eps {gd['eps']}, weight_decay "
-                    f"{gd.get('weight_decay', 0)} against {self.hp['betas']}, {self.hp['eps']}, 0")
-            self.hp["lr_D"] = float(gd["lr"])
-
-    def set_rng_rank(self, rank, world):
-        """Key the device draws by the global batch's rows (data parallelism)."""
-        rank, world = int(rank), int(world)
-        if world < 1 or not 0 <= rank < world:
-            raise ValueError(f"rng rank {rank} of {world}")
-        self.rng_rank, self.rng_world = rank, world
 
     # gradients that are final before the feature backward: g_grad[G_FC1_W:] and
     # all of D, contiguous in grad_flat (part 1 of a split step)
@@ -338,43 +437,18 @@ class AdvTrainStep:
         (part 1: g_param[G_LATE_END:] and D; part 2: g_param[:G_LATE_END])."""
         a = AdvArgs()
         a.part = int(part)
-        a.g_param, a.g_grad = self.g_param.data_ptr(), self.g_grad.data_ptr()
-        a.g_m, a.g_v = self.g_m.data_ptr(), self.g_v.data_ptr()
-        a.d_param, a.d_grad = self.d_param.data_ptr(), self.d_grad.data_ptr()
-        a.d_m, a.d_v = self.d_m.data_ptr(), self.d_v.data_ptr()
-        a.step_count = self.step_count.data_ptr()
-        a.lr_g, a.lr_d = self.hp["lr"], self.hp["lr_D"]
-        a.beta1, a.beta2, a.eps = self.hp["betas"][0], self.hp["betas"][1], self.hp["eps"]
+        self._fill_state(a)
         check(self.lib.pcadv_adv_step_adam(ctypes.byref(a), stream_ptr()), "pcadv_adv_step_adam")
 
     # ------------------------------------------------------------------
-    def _snapshot(self):
-        return [t.clone() for t in (self.g_param, self.g_m, self.g_v, self.d_param, self.d_m,
-                                    self.d_v, self.step_count)]
-
-    def _restore(self, saved):
-        for dst, src in zip((self.g_param, self.g_m, self.g_v, self.d_param, self.d_m, self.d_v,
-                             self.step_count), saved):
-            dst.copy_(src)
-
     def capture_on(self, pts_gt, labels, pts_nogt, apply_adam=True, semi=False, part=0):
         """Capture one step (or one part of it) reading the given (resident)
         input buffers into a HIP graph; state is left as it was before the
-        capture."""
-        saved = self._snapshot()
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up: the whole step (part 2 needs part 1's state)
-            self(pts_gt, labels, pts_nogt, apply_adam=apply_adam, semi=semi)
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        a = self._args(pts_gt, labels, pts_nogt, None, None, apply_adam, semi, part)
-        self._keep.append(a)
-        with torch.cuda.graph(g):
-            check(self.lib.pcadv_adv_step(ctypes.byref(a), stream_ptr()), "pcadv_adv_step (capture)")
-        torch.cuda.synchronize()
-        self._restore(saved)
-        return g
+        capture.  The warm-up is the whole step (part 2 needs part 1's state)."""
+        return self._capture_launches(
+            lambda: self(pts_gt, labels, pts_nogt, apply_adam=apply_adam, semi=semi),
+            self.lib.pcadv_adv_step, "pcadv_adv_step (capture)",
+            [self._args(pts_gt, labels, pts_nogt, None, None, apply_adam, semi, part)])
 
     def capture_seq(self, batches, apply_adam=True):
         """Capture len(batches) consecutive steps, step i reading the resident
@@ -382,21 +456,10 @@ class AdvTrainStep:
         device step counter advances per step, so each draws its own dropout
         masks and D labels).  One replay = len(batches) iterations with one
         graph-launch overhead; state is left as it was before the capture."""
-        saved = self._snapshot()
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self(*batches[0], apply_adam=apply_adam)
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        args = [self._args(pg, lab, pn, None, None, apply_adam, False, 0) for pg, lab, pn in batches]
-        self._keep.extend(args)
-        with torch.cuda.graph(g):
-            for a in args:
-                check(self.lib.pcadv_adv_step(ctypes.byref(a), stream_ptr()), "pcadv_adv_step (capture)")
-        torch.cuda.synchronize()
-        self._restore(saved)
-        return g
+        return self._capture_launches(
+            lambda: self(*batches[0], apply_adam=apply_adam),
+            self.lib.pcadv_adv_step, "pcadv_adv_step (capture)",
+            [self._args(pg, lab, pn, None, None, apply_adam, False, 0) for pg, lab, pn in batches])
 
     def capture(self):
         """Capture one step over static input buffers; returns the buffers
@@ -423,42 +486,13 @@ class AdvTrainStep:
             return self.workspace[:2 * n].view(torch.bfloat16).view(C, N, 128)
         return self.workspace[:4 * n].view(torch.float32).view(C, N, 128)
 
-    def sync_optimizer_state(self):
-        """Copy the device step counter into the torch optimizers' 'step'."""
-        t = float(self.step_count.item())
-        for opt in self.optimizers:
-            set_optimizer_step(opt, t)
-
-    def after_torch_step(self):
-        """After an iteration the trainer ran through autograd and the torch
-        optimizers (unequal GT / no-GT batches): the device step counter
-        advances with torch's, and each p.grad (a fresh tensor after
-        zero_grad + backward) is copied back into the flat gradient buffer
-        and rebound as its view."""
-        self.step_count += 1
-        for opt, mod, m, v, gr, layout in self._bind:
-            gv = _views(gr, mod, layout)
-            for name, p in mod.named_parameters():
-                if p.grad is None:
-                    gv[name].zero_()  # no gradient this iteration: not the last fused one's
-                elif p.grad.data_ptr() != gv[name].data_ptr():
-                    gv[name].copy_(p.grad)
-                p.grad = gv[name]
-
 
 def ft_layout(model):
     """Flat layout of a PointNetCls(feature_transform=True): the plain
     generator's tensors at their include/pcadv.h offsets (so the fused tail's
     fc1..fc3 offsets hold), then the STNkd(64) parameters in state_dict order,
     each 256-B aligned.  Returns (layout, numel)."""
-    layout = dict(G_LAYOUT)
-    off = (G_NUMEL + 63) // 64 * 64
-    for name, p in model.named_parameters():
-        if name in layout:
-            continue
-        layout[name] = off
-        off += (p.numel() + 63) // 64 * 64
-    return layout, off
+    return sequential_layout(model, G_LAYOUT, pad64(G_NUMEL))
 
 
 def _ft_extractor_forward(P, pts, N):
@@ -552,7 +586,7 @@ def _ft_extractor_backward(P, Gr, act, pts, dgmax, N, dT_hook=None):
     ops.pw_wgrad_finish(jobs)
 
 
-class AdvFtTrainStep(AdvTrainStep):
+class AdvFtTrainStep(_FtExtractor, AdvTrainStep):
     """run_training's iteration (utils/trainer.py:426-559) with a
     PointNetCls(k=40, feature_transform=True) generator + DeepConvDiscNet(40, 1)
     (VERDICT r05 item 4), without autograd:
@@ -578,88 +612,16 @@ class AdvFtTrainStep(AdvTrainStep):
     iteration, checkpoints and the torch optimizers' state work unchanged."""
 
     supports_parts = False
+    _no_ft = "the generator has no feature transform (use AdvTrainStep)"
 
     def __init__(self, model, model_D, B, N, optimizer=None, optimizer_D=None, lr=1e-4,
                  lr_D=1e-4, betas=(0.9, 0.999), eps=1e-8, lambda_cls=1.0, lambda_adv=0.001,
                  seed=0, device="cuda", lambda_semi=1.0, semi_th=0.8, rng_rank=0, rng_world=1):
-        self.lib = _lib.load()
-        if not getattr(model, "feature_transform", False):
-            raise ValueError("AdvFtTrainStep: the generator has no feature transform "
-                             "(use AdvTrainStep)")
-        self.set_rng_rank(rng_rank, rng_world)
-        self.model, self.model_D = model, model_D
-        self.precision = 0
-        self.B, self.N = int(B), int(N)
-        if self.N % 128:
-            # the per-cloud transform x2 T and its dT = x2^T dx2t run on 64- / 128-row
-            # tiles (pcadv_pw_fwd rows_per_w, pcadv_pw_bwd_weight rows_per_group)
-            raise ValueError(f"AdvFtTrainStep: N = {self.N} points, a multiple of 128 is required")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("AdvFtTrainStep runs on the HIP device only")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        if optimizer is not None:
-            g = optimizer.param_groups[0]
-            lr, betas, eps = g["lr"], tuple(g["betas"]), g["eps"]
-        if optimizer_D is not None:
-            lr_D = optimizer_D.param_groups[0]["lr"]
-        self.hp = dict(lr=float(lr), lr_D=float(lr_D), betas=tuple(float(b) for b in betas),
-                       eps=float(eps), lambda_cls=float(lambda_cls),
-                       lambda_adv=float(lambda_adv), p=float(model.dropout.p),
-                       lambda_semi=float(lambda_semi), semi_th=float(semi_th))
-        self.layout, self.g_numel = ft_layout(model)
-        self.g_param = flatten_params(model, self.layout, self.g_numel, dev)
-        self.d_param = flatten_params(model_D, D_LAYOUT, D_NUMEL, dev)
-        d_off = (self.g_numel + 63) // 64 * 64
-        self.grad_flat = torch.zeros(d_off + D_NUMEL, device=dev)
-        self.g_grad = self.grad_flat[:self.g_numel]
-        self.d_grad = self.grad_flat[d_off:]
-        self.g_m = torch.zeros_like(self.g_param)
-        self.g_v = torch.zeros_like(self.g_param)
-        self.d_m = torch.zeros_like(self.d_param)
-        self.d_v = torch.zeros_like(self.d_param)
-        t0 = max(_adopt_adam_state(optimizer, model, self.g_m, self.g_v, self.layout),
-                 _adopt_adam_state(optimizer_D, model_D, self.d_m, self.d_v, D_LAYOUT))
-        self.step_count = torch.full((1,), t0, device=dev, dtype=torch.int32)
-        self._bind = ((optimizer, model, self.g_m, self.g_v, self.g_grad, self.layout),
-                      (optimizer_D, model_D, self.d_m, self.d_v, self.d_grad, D_LAYOUT))
-        for args_ in self._bind:
-            _bind_adam_state(*args_, t0)
-        self.optimizers = (optimizer, optimizer_D)
-        self.losses = torch.zeros(6, device=dev)
-        self.logits = torch.zeros(2 * self.B, 40, device=dev)
-        nbytes = self.lib.pcadv_adv_step_workspace_bytes(self.B, self.N)
-        self.workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.graph = None
-        self._keep = []
-        C = 2 * self.B
-        self.pts = torch.empty(C, self.N, 3, device=dev)     # [GT; no-GT] clouds
-        self.dgmax = torch.empty(C, 1024, device=dev)
-        self._p = dict(model.named_parameters())
-        self._g = _views(self.g_grad, model, self.layout)
-
-    # the trainer's graphed iteration folds its gathers / epilogue into the
-    # step; here they are this call's first and last launches
-    def _pre(self):
-        if self._gather is not None:
-            check(self.lib.pcadv_gather_clouds_multi(self._gather, len(self._gather),
-                                                     stream_ptr()), "pcadv_gather_clouds_multi")
-
-    def _post(self):
-        if self._epilogue is None:
-            return
-        counters, n, ring = self._epilogue
-        P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        if ring is None:
-            check(self.lib.pcadv_iter_epilogue(P(counters), n, None, 0, None, 0, None,
-                                               stream_ptr()), "pcadv_iter_epilogue")
-        else:
-            check(self.lib.pcadv_iter_epilogue(P(counters), n, P(self.losses), ring.nl,
-                                               P(ring.ring), ring.slots, P(ring.count),
-                                               stream_ptr()), "pcadv_iter_epilogue")
+        super().__init__(model, model_D, B, N, optimizer, optimizer_D, lr, lr_D, betas, eps,
+                         lambda_cls, lambda_adv, seed, device, lambda_semi, semi_th, "fp32",
+                         rng_rank, rng_world)
+        self._init_ft(2 * self.B)
+        self.pts = torch.empty(2 * self.B, self.N, 3, device=self.device)  # [GT; no-GT] clouds
 
     def __call__(self, pts_gt, labels, pts_nogt, masks=None, soft=None, apply_adam=True,
                  semi=False, part=0):
@@ -714,27 +676,15 @@ class AdvFtTrainStep(AdvTrainStep):
     def capture_on(self, pts_gt, labels, pts_nogt, apply_adam=True, semi=False, part=0):
         """One iteration over resident input buffers as a HIP graph (state left
         as it was before the capture)."""
-        saved = self._snapshot()
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        def body():
             self(pts_gt, labels, pts_nogt, apply_adam=apply_adam, semi=semi)
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self(pts_gt, labels, pts_nogt, apply_adam=apply_adam, semi=semi)
-        torch.cuda.synchronize()
-        self._restore(saved)
-        return g
-
-    def capture_seq(self, batches, apply_adam=True):
-        raise NotImplementedError("AdvFtTrainStep: one iteration per graph")
+        return self._capture(body, body)
 
     def saved_x3(self):
         raise NotImplementedError("AdvFtTrainStep keeps no x3 in its workspace")
 
 
-class ClsTrainStep:
+class ClsTrainStep(_ModelNetStep):
     """run_training_pointnet_cls's iteration (utils/trainer.py:222-268) for
     PointNetCls(k=40, feature_transform=False): forward on B labelled clouds,
     lambda_cls * CrossEntropyLoss, backward, Adam - one pcadv_cls_step call
@@ -743,69 +693,20 @@ class ClsTrainStep:
     precision="bf16": the feature forward's conv3 / conv4 on bf16-rounded
     operands (configs[1] is quoted in bf16); everything else f32."""
 
-    _epilogue = None  # (counters, ncounters, _LossRing) folded into the last launch
-    _gather = None    # ctypes GatherJob array gathered by the first launch
-
-    @contextlib.contextmanager
-    def folded_epilogue(self, counters=None, ncounters=0, ring=None):
-        """Within the block every step call also runs the training iteration's
-        epilogue (counters[:ncounters] += 1, the losses into the loss ring; as
-        pcadv_iter_epilogue) inside its own finishing launch - one launch less
-        per graph-replayed iteration (pcadv_adv_args.epi_*)."""
-        self._epilogue = (counters, int(ncounters), ring)
-        try:
-            yield
-        finally:
-            self._epilogue = None
-
-    @contextlib.contextmanager
-    def folded_gather(self, jobs):
-        """Within the block every step call gathers its own input batches in
-        its first launch (pcadv_adv_args.gather: the loaders' gather_at jobs,
-        DeviceCloudLoader._gather_job, whose outputs are the step's inputs) -
-        the iteration's gather launch disappears."""
-        self._gather = (_lib.GatherJob * len(jobs))(*jobs)
-        try:
-            yield
-        finally:
-            self._gather = None
+    _nlosses = 1
 
     def __init__(self, model, B, N, optimizer=None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  lambda_cls=1.0, seed=0, device="cuda", precision="fp32", rng_rank=0, rng_world=1):
-        self.lib = _lib.load()
-        self.set_rng_rank(rng_rank, rng_world)
-        self.model = model
         self.precision = _precision(precision)
-        self.B, self.N = int(B), int(N)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("ClsTrainStep runs on the HIP device only")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
+        super().__init__(model, None, B, N, (optimizer,), (lr,), betas, eps,
+                         dict(lambda_cls=float(lambda_cls)), self._nlosses, seed, device,
+                         rng_rank, rng_world)
+
+    def _layout(self, model, N):
         if getattr(model, "feature_transform", False):
             raise NotImplementedError("ClsTrainStep: feature_transform=True trains through "
                                       "run_training_pointnet_cls's autograd path")
-        if optimizer is not None:
-            g = optimizer.param_groups[0]
-            lr, betas, eps = g["lr"], tuple(g["betas"]), g["eps"]
-        self.hp = dict(lr=float(lr), betas=betas, eps=float(eps), lambda_cls=float(lambda_cls),
-                       p=float(model.dropout.p))
-        self.g_param = flatten_params(model, G_LAYOUT, G_NUMEL, dev)
-        self.g_grad = torch.zeros(G_NUMEL, device=dev)
-        self.g_m = torch.zeros_like(self.g_param)
-        self.g_v = torch.zeros_like(self.g_param)
-        t0 = _adopt_adam_state(optimizer, model, self.g_m, self.g_v, G_LAYOUT)
-        self.step_count = torch.full((1,), t0, device=dev, dtype=torch.int32)
-        _bind_adam_state(optimizer, model, self.g_m, self.g_v, self.g_grad, G_LAYOUT, t0)
-        self._bind = ((optimizer, model, self.g_m, self.g_v, self.g_grad, G_LAYOUT),)
-        self.optimizer = optimizer
-        self.losses = torch.zeros(1, device=dev)
-        self.logits = torch.zeros(self.B, 40, device=dev)
-        nbytes = self.lib.pcadv_adv_step_workspace_bytes(self.B, self.N)
-        self.workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self._keep = []
+        return super()._layout(model, N)
 
     def _args(self, pts, labels, mask, apply_adam):
         B, N = int(pts.shape[0]), self.N
@@ -823,12 +724,8 @@ class ClsTrainStep:
             if tuple(mask.shape) != (B, 256) or mask.dtype != torch.float32 or not mask.is_contiguous():
                 raise ValueError("dropout mask must be contiguous float32 (B, 256)")
             a.drop_mask_gt = mask.data_ptr()
-        a.g_param, a.g_grad = self.g_param.data_ptr(), self.g_grad.data_ptr()
-        a.g_m, a.g_v = self.g_m.data_ptr(), self.g_v.data_ptr()
-        a.step_count = self.step_count.data_ptr()
-        hp = self.hp
-        a.lr_g, a.beta1, a.beta2, a.eps = hp["lr"], hp["betas"][0], hp["betas"][1], hp["eps"]
-        a.lambda_cls, a.drop_p = hp["lambda_cls"], hp["p"]
+        self._fill_state(a)
+        a.lambda_cls, a.drop_p = self.hp["lambda_cls"], self.hp["p"]
         a.rng_seed = self.seed
         a.apply_adam = int(bool(apply_adam))
         a.losses = self.losses.data_ptr()
@@ -840,9 +737,6 @@ class ClsTrainStep:
         _fill_epilogue(a, self._epilogue, self._gather)
         return a
 
-    set_rng_rank = AdvTrainStep.set_rng_rank
-    sync_hyper = AdvTrainStep.sync_hyper
-
     def __call__(self, pts, labels, mask=None, apply_adam=True):
         a = self._args(pts, labels, mask, apply_adam)
         check(self.lib.pcadv_cls_step(ctypes.byref(a), stream_ptr()), "pcadv_cls_step")
@@ -850,50 +744,16 @@ class ClsTrainStep:
 
     def capture_on(self, pts, labels):
         """A HIP graph of one step over resident buffers (state restored)."""
-        saved = [t.clone() for t in (self.g_param, self.g_m, self.g_v, self.step_count)]
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self(pts, labels)
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        a = self._args(pts, labels, None, True)
-        self._keep.append(a)
-        with torch.cuda.graph(g):
-            check(self.lib.pcadv_cls_step(ctypes.byref(a), stream_ptr()), "pcadv_cls_step (capture)")
-        torch.cuda.synchronize()
-        for dst, src in zip((self.g_param, self.g_m, self.g_v, self.step_count), saved):
-            dst.copy_(src)
-        return g
+        return self.capture_seq([(pts, labels)])
 
     def capture_seq(self, batches):
         """len(batches) consecutive steps (batches[i] = (pts, labels)) in ONE
         HIP graph, as AdvTrainStep.capture_seq (state restored)."""
-        saved = [t.clone() for t in (self.g_param, self.g_m, self.g_v, self.step_count)]
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self(*batches[0])
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        args = [self._args(pts, lab, None, True) for pts, lab in batches]
-        self._keep.extend(args)
-        with torch.cuda.graph(g):
-            for a in args:
-                check(self.lib.pcadv_cls_step(ctypes.byref(a), stream_ptr()), "pcadv_cls_step (capture)")
-        torch.cuda.synchronize()
-        for dst, src in zip((self.g_param, self.g_m, self.g_v, self.step_count), saved):
-            dst.copy_(src)
-        return g
+        return self._capture_launches(
+            lambda: self(*batches[0]), self.lib.pcadv_cls_step, "pcadv_cls_step (capture)",
+            [self._args(pts, lab, None, True) for pts, lab in batches])
 
-    def sync_optimizer_state(self):
-        if self.optimizer is not None:
-            set_optimizer_step(self.optimizer, float(self.step_count.item()))
-
-    after_torch_step = AdvTrainStep.after_torch_step
-
-
-class ClsFtTrainStep(ClsTrainStep):
+class ClsFtTrainStep(_FtExtractor, ClsTrainStep):
     """run_training_pointnet_cls's iteration (utils/trainer.py:222-268) with
     PointNetCls(k=40, feature_transform=True), without autograd: the
     extractor's forward on the point-wise kernels (_ft_extractor_forward: two
@@ -906,58 +766,21 @@ class ClsFtTrainStep(ClsTrainStep):
     gradients and Adam moments are flat buffers in ft_layout order bound to
     the model and optimizer as ClsTrainStep's."""
 
+    _no_ft = "the model has no feature transform (use ClsTrainStep)"
+    _nlosses = 2  # [loss_cls, loss_regu]
+
     def __init__(self, model, B, N, optimizer=None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  lambda_cls=1.0, lambda_regu=0.001, seed=0, device="cuda", rng_rank=0,
                  rng_world=1):
-        self.lib = _lib.load()
-        self.set_rng_rank(rng_rank, rng_world)
-        if not getattr(model, "feature_transform", False):
-            raise ValueError("ClsFtTrainStep: the model has no feature transform (use ClsTrainStep)")
-        self.model = model
-        self.precision = 0
-        self.B, self.N = int(B), int(N)
-        if self.N % 128:
-            raise ValueError(f"ClsFtTrainStep: N = {self.N} points, a multiple of 128 is required")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("ClsFtTrainStep runs on the HIP device only")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        if optimizer is not None:
-            g = optimizer.param_groups[0]
-            lr, betas, eps = g["lr"], tuple(g["betas"]), g["eps"]
-        self.hp = dict(lr=float(lr), betas=tuple(float(b) for b in betas), eps=float(eps),
-                       lambda_cls=float(lambda_cls), p=float(model.dropout.p))
-        self.layout, self.g_numel = ft_layout(model)
-        self.g_param = flatten_params(model, self.layout, self.g_numel, dev)
-        self.g_grad = torch.zeros(self.g_numel, device=dev)
-        self.g_m = torch.zeros_like(self.g_param)
-        self.g_v = torch.zeros_like(self.g_param)
-        t0 = _adopt_adam_state(optimizer, model, self.g_m, self.g_v, self.layout)
-        self.step_count = torch.full((1,), t0, device=dev, dtype=torch.int32)
-        _bind_adam_state(optimizer, model, self.g_m, self.g_v, self.g_grad, self.layout, t0)
-        self._bind = ((optimizer, model, self.g_m, self.g_v, self.g_grad, self.layout),)
-        self.optimizer = optimizer
-        self.losses = torch.zeros(2, device=dev)  # [loss_cls, loss_regu]
-        self.logits = torch.zeros(self.B, 40, device=dev)
-        nbytes = self.lib.pcadv_adv_step_workspace_bytes(self.B, self.N)
-        self.workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self._keep = []
-        self.dgmax = torch.empty(self.B, 1024, device=dev)
-        self._norms = torch.empty(self.B, device=dev)
-        self._lregu = torch.full((1,), float(lambda_regu), device=dev)
-        self._p = dict(model.named_parameters())
-        self._g = _views(self.g_grad, model, self.layout)
+        super().__init__(model, B, N, optimizer, lr, betas, eps, lambda_cls, seed, device, "fp32",
+                         rng_rank, rng_world)
+        self._init_ft(self.B)
+        self._norms = torch.empty(self.B, device=self.device)
+        self._lregu = torch.full((1,), float(lambda_regu), device=self.device)
 
     @property
     def lambda_regu(self):
         return float(self._lregu.item())
-
-    # gathers / epilogue as this call's own first and last launches
-    _pre = AdvFtTrainStep._pre
-    _post = AdvFtTrainStep._post
 
     def __call__(self, pts, labels, mask=None, apply_adam=True):
         a = self._args(pts, labels, mask, False)
@@ -1000,19 +823,6 @@ class ClsFtTrainStep(ClsTrainStep):
 
     def capture_on(self, pts, labels):
         """One iteration over resident buffers as a HIP graph (state restored)."""
-        saved = [t.clone() for t in (self.g_param, self.g_m, self.g_v, self.step_count)]
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        def body():
             self(pts, labels)
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self(pts, labels)
-        torch.cuda.synchronize()
-        for dst, src in zip((self.g_param, self.g_m, self.g_v, self.step_count), saved):
-            dst.copy_(src)
-        return g
-
-    def capture_seq(self, batches):
-        raise NotImplementedError("ClsFtTrainStep: one iteration per graph")
+        return self._capture(body, body)

@@ -23,9 +23,9 @@ import torch.nn.functional as F
 from .discriminator import DeepConvDiscNet
 from .metric import batch_get_iou, object_names
 from .pointnet import PointNetCls, feature_transform_regularizer
-from ._lib import D_LAYOUT
 from .dataset import gather_at_multi
-from .step import AdvFtTrainStep, AdvTrainStep, _views
+from .flat import capture_graphs
+from .step import AdvFtTrainStep, AdvTrainStep
 from .utils import make_D_label
 
 
@@ -199,20 +199,6 @@ def _opt_hyper(opts):
                   f(g.get("weight_decay", 0.0))) for o in opts for g in o.param_groups)
 
 
-def _detached_snapshot(state):
-    """Copies of the tensors a capture's warm-up changes.  Detached, under
-    no_grad: a clone of a parameter made with grad mode on would hold its
-    AccumulateGrad node (created on the launching stream) alive into the
-    capture, where it then runs on the wrong stream (the HIP runtime crashed
-    at capture end).  Checked, so a future state list cannot bring it back."""
-    with torch.no_grad():
-        saved = [t.detach().clone() for t in state]
-    bad = [i for i, t in enumerate(saved) if t.grad_fn is not None or t.requires_grad]
-    if bad:
-        raise RuntimeError(f"capture state snapshot {bad} carries autograd history")
-    return saved
-
-
 class _GraphedIteration:
     """One training iteration fed by DeviceCloudLoaders as ONE HIP graph: each
     loader's batch gathered (+ device jitter) into static input buffers from a
@@ -295,7 +281,7 @@ class _GraphedIteration:
         the iteration epilogue in their last: the graph is the step's launches
         alone."""
         st = self.step
-        if not hasattr(st, "folded_gather") or self.lab.shape[1] != 1:
+        if not st.folds_iteration or self.lab.shape[1] != 1:
             return None
         stack = contextlib.ExitStack()
         stack.enter_context(st.folded_gather(self._gather_jobs()))
@@ -315,27 +301,17 @@ class _GraphedIteration:
         if fold is None:
             self.ring.write(self.step.losses, self.counters, 2 * L)
 
+    def _capture(self, semi):
+        """This iteration's graph(s); the warm-up runs outside the capture."""
+        def body():
+            self._body(semi)
+        return capture_graphs(self.step.device, body, body, self._state())
+
     def _graph(self, semi):
         g = self.graphs.get(semi)
         if g is None:
-            st = self.step
-            state = self._state()
-            saved = _detached_snapshot(state)
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream(device=st.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):  # warm-up outside the capture
-                self._body(semi)
-            cur.wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._body(semi)
-            torch.cuda.synchronize()
-            with torch.no_grad():
-                for dst, src in zip(state, saved):
-                    dst.copy_(src)
-            if hasattr(st, "after_capture"):
-                st.after_capture()
+            g = self._capture(semi)
+            self.step.after_capture()
             self.graphs[semi] = g
         return g
 
@@ -343,8 +319,7 @@ class _GraphedIteration:
         h = _opt_hyper(self.optimizers)
         if h != self._hyper:
             self.graphs.clear()
-            if hasattr(self.step, "sync_hyper"):
-                self.step.sync_hyper()
+            self.step.sync_hyper()
             self._hyper = h
 
     def replay(self, semi=False):
@@ -353,14 +328,7 @@ class _GraphedIteration:
         return self.step.losses
 
     def _state(self):
-        st = self.step
-        if hasattr(st, "graph_state"):  # a step that names its own state
-            pre = st.graph_state()
-        else:
-            pre = [t for t in (getattr(st, n, None) for n in
-                               ("g_param", "g_m", "g_v", "d_param", "d_m", "d_v", "step_count"))
-                   if t is not None]
-        return pre + [self.counters, self.ring.count, self.ring.ring]
+        return self.step.graph_state() + [self.counters, self.ring.count, self.ring.ring]
 
 
 class _DPIteration(_GraphedIteration):
@@ -388,7 +356,7 @@ class _DPIteration(_GraphedIteration):
     def _part(self, k, semi):
         st, L = self.step, self.L
         if k == 1:
-            if hasattr(st, "folded_gather"):
+            if st.folds_iteration:
                 with st.folded_gather(self._gather_jobs()):
                     st(self.pts[0], self.lab[:, 0], self.pts[1], apply_adam=False, semi=semi)
             else:
@@ -410,36 +378,13 @@ class _DPIteration(_GraphedIteration):
         self._average()
         self._part(2, semi)
 
-    def _graph(self, semi):
-        gs = self.graphs.get(semi)
-        if gs is None:
-            state = self._state()
-            saved = _detached_snapshot(state)
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream(device=self.step.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):  # warm-up outside the capture (every rank alike)
-                self._whole(semi)
-            cur.wait_stream(side)
-            torch.cuda.synchronize()
-            if self.captured:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._whole(semi)
-                gs = [g]
-            else:
-                gs = []
-                for k in (1, 2):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        self._part(k, semi)
-                    gs.append(g)
-            torch.cuda.synchronize()
-            with torch.no_grad():
-                for dst, src in zip(state, saved):
-                    dst.copy_(src)
-            self.graphs[semi] = gs
-        return gs
+    def _capture(self, semi):
+        # one warm-up of the whole iteration (every rank alike), a device
+        # synchronize for its collectives, then one graph or the two around them
+        captures = ([lambda: self._whole(semi)] if self.captured
+                    else [lambda: self._part(1, semi), lambda: self._part(2, semi)])
+        return capture_graphs(self.step.device, lambda: self._whole(semi), captures,
+                              self._state(), sync_before_capture=True)
 
     def replay(self, semi=False):
         self._check_hyper()
@@ -496,6 +441,11 @@ class _AutogradStep:
     (allocated once, from the graph's pool) instead of adding it into a zeroed
     one, which would replay one add kernel per parameter (28 of them, about
     0.11 ms of the feature-transform cls step)."""
+
+    folds_iteration = False  # the iteration gathers and writes its epilogue itself
+
+    def sync_hyper(self):
+        """Nothing to re-read: the torch optimizers hold their hyperparameters."""
 
     def _params(self):
         return [p for o in self.opts for g in o.param_groups for p in g["params"]]
@@ -699,9 +649,8 @@ def _pooled_d_grads(step, model_D, gan_loss, pool_gt, pool_nogt, B, device):
     d_out = model_D(pool_nogt.query(logp[B:].detach()))
     loss_d2 = gan_loss(d_out, make_D_label(d_out, 0, device, random=True)) * 0.5
     loss_d2.backward()
-    views = _views(step.d_grad, model_D, D_LAYOUT)
-    for name, p in model_D.named_parameters():
-        if p.grad is None or p.grad.data_ptr() != views[name].data_ptr():
+    for (name, p), view in zip(model_D.named_parameters(), step.nets[1].grad_views):
+        if p.grad is None or p.grad.data_ptr() != view.data_ptr():
             raise RuntimeError(f"D parameter {name}: .grad is no longer a view of the fused "
                                "step's gradient buffer")
     step.losses[2:4].copy_(torch.stack((loss_d1.detach(), loss_d2.detach())))
@@ -1245,125 +1194,11 @@ def _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
 
 
 def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, pool_gt, pool_nogt,
-                  pts, cls, seg, pts_nogt, cls_nogt, args):
-    """utils/trainer.py:881-966 through autograd over the same modules."""
-    optimizer.zero_grad()
-    optimizer_D.zero_grad()
-    for param in model_D.parameters():  # train G
-        param.requires_grad = False
-    pred, _ = model(pts, cls)
-    l_seg = seg_loss(pred, seg)
-    pred_gt_softmax = F.softmax(pred, dim=1)
-    pred_nogt, _ = model(pts_nogt, cls_nogt)
-    pred_nogt_softmax = F.log_softmax(pred_nogt, dim=1)
-    D_out = model_D(pred_nogt_softmax)
-    loss_adv = gan_loss(D_out, make_D_label(input=D_out, value=1, device=args.device, random=False))
-    (args.lambda_seg * l_seg + args.lambda_adv * loss_adv).backward()
-    for param in model_D.parameters():  # train D
-        param.requires_grad = True
-    loss_D_value = 0.0
-    for pool, x, value in ((pool_gt, pred_gt_softmax, 1), (pool_nogt, pred_nogt_softmax, 0)):
-        D_out = model_D(pool.query(x.detach()))
-        loss_D = 0.5 * gan_loss(D_out, make_D_label(input=D_out, value=value, device=args.device,
-                                                    random=True))
-        loss_D.backward()
-        loss_D_value += loss_D.item()
-    optimizer.step()
-    optimizer_D.step()
-    return [l_seg.item(), loss_adv.item(), loss_D_value]
-
-
-def run_training_seg(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetloader_nogt_iter,
-                     testloader, testdataset, model, model_D, gan_loss, seg_loss, optimizer,
-                     optimizer_D, history_pool_gt, history_pool_nogt, train_logger, test_logger,
-                     writer, args):
-    """utils/trainer.py:849-1026: adversarial segmentation with the per-point
-    discriminator.  With PointNetSeg + PointwiseDiscNet, two plain Adams,
-    CrossEntropyLoss + BCEWithLogitsLoss and ImagePool(0) on the HIP device,
-    every iteration whose two batches have the same shape is one
-    SegAdvTrainStep; any other configuration, and a ragged last batch, runs the
-    reference's body through autograd over the same modules."""
-    from .seg import SegAdvTrainStep
-    max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
-    max_train_epoch = max_train_cat_epoch = max_train_all_epoch = 0
-    fusable = _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                               history_pool_gt, history_pool_nogt, args)
-    step, eager_since = None, False
-    tb = getattr(args, "tensorboard", False) and writer is not None
-
-    def save(tag):
-        if step is not None:
-            step.sync_optimizer_state()
-        torch.save(model.state_dict(), os.path.join(args.exp_dir, "model_train_{}.pth".format(tag)))
-        torch.save(model_D.state_dict(), os.path.join(args.exp_dir, "modelD_train_{}.pth".format(tag)))
-
-    for i_iter in range(args.total_iterations):
-        model.train()
-        model_D.train()
-        batch, trainloader_gt_iter = _next(trainloader_gt, trainloader_gt_iter)
-        pts, cls, seg = batch
-        pts, cls, seg = pts.float().to(args.device), cls.float().to(args.device), \
-            seg.long().to(args.device)
-        batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
-        pts_nogt, cls_nogt = batch
-        pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
-        if fusable and pts.shape == pts_nogt.shape \
-                and (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0:
-            if step is None:
-                step = SegAdvTrainStep(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
-                                       lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
-                                       device=args.device, seed=int(getattr(args, "seed", 0) or 0))
-            elif eager_since:
-                step.after_eager()
-            eager_since = False
-            step.sync_hyper()
-            vals = step(pts.contiguous(), cls.contiguous(), seg.contiguous(),
-                        pts_nogt.contiguous(), cls_nogt.contiguous()).tolist()
-        else:
-            if step is not None:
-                step.sync_optimizer_state()
-            eager_since = True
-            vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                                 history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
-                                 cls_nogt, args)
-        train_logger.info('iter = {0:8d}/{1:8d} '
-                          'loss_seg = {2:.3f} '
-                          'loss_adv = {3:.3f} '
-                          'loss_D = {4:.3f} '.format(i_iter, args.total_iterations, *vals))
-        if tb:
-            writer.add_scalar('Loss/train_seg', vals[0], i_iter)
-            writer.add_scalar('Loss/train_adv', vals[1], i_iter)
-            writer.add_scalar('Loss/train_disc', vals[2], i_iter)
-        if i_iter % args.iter_test_epoch == 0:
-            save("epoch_{}".format(i_iter // args.iter_test_epoch))
-            accu, _, cat_iou, all_iou = run_testing_seg(
-                dataloader=testloader, dataset=testdataset, model=model, criterion=seg_loss,
-                logger=test_logger, test_iter=i_iter, writer=writer, args=args)
-            ep = i_iter // args.iter_test_epoch
-            if max_seg_accu < accu:
-                max_seg_accu, max_train_epoch = accu, ep
-                save("best")
-            if max_test_cat_iou < cat_iou:
-                max_test_cat_iou, max_train_cat_epoch = cat_iou, ep
-                save("best_cat_iou")
-            if max_test_all_iou < all_iou:
-                max_test_all_iou, max_train_all_epoch = all_iou, ep
-                save("best_all_iou")
-    if step is not None:
-        step.sync_optimizer_state()
-    train_logger.info("=========================")
-    train_logger.info("Max accuracy: {:.4f}, at epoch: {}".format(max_seg_accu, max_train_epoch))
-    train_logger.info("Max cat mIoU: {:.4f}, at epoch: {}".format(max_test_cat_iou, max_train_cat_epoch))
-    train_logger.info("Max all mIoU: {:.4f}, at epoch: {}".format(max_test_all_iou, max_train_all_epoch))
-    if tb:
-        writer.close()
-    return max_seg_accu, max_test_cat_iou, max_test_all_iou
-
-
-def _seg_semi_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, semi_loss, pool_gt,
-                   pool_nogt, pts, cls, seg, pts_nogt, cls_nogt, semi, args):
-    """utils/trainer.py:1956-2061 through autograd over the same modules; `semi`
-    is the iteration's (args.semi_start > 0 and i_iter > args.semi_start)."""
+                  pts, cls, seg, pts_nogt, cls_nogt, args, semi_loss=None, semi=False):
+    """utils/trainer.py:881-966 through autograd over the same modules: returns
+    [loss_seg, loss_adv, loss_D].  With a semi_loss, :1956-2061: `semi` is the
+    iteration's (args.semi_start > 0 and i_iter > args.semi_start) and the
+    values are [loss_seg, loss_adv, loss_semi, loss_D]."""
     optimizer.zero_grad()
     optimizer_D.zero_grad()
     for param in model_D.parameters():  # train G
@@ -1397,30 +1232,40 @@ def _seg_semi_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, s
         loss_D_value += loss_D.item()
     optimizer.step()  # the reference steps G before D's part: D is frozen there, the same values
     optimizer_D.step()
+    if semi_loss is None:
+        return [l_seg.item(), loss_adv.item(), loss_D_value]
     return [l_seg.item(), loss_adv.item(), loss_semi_value, loss_D_value]
 
 
-def run_training_seg_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
-                          targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
-                          seg_loss, semi_loss, optimizer, optimizer_D, history_pool_gt,
-                          history_pool_nogt, train_logger, test_logger, writer, args):
-    """utils/trainer.py:1903-2121: run_training_seg plus, for i_iter >
-    args.semi_start (> 0), lambda_semi x semi_loss(pred_nogt, argmax(pred_nogt))
-    over the no-GT points the frozen discriminator scores above args.semi_TH
-    (the rest are ignore_index 255).  In run_training_seg's fused configuration,
-    with CrossEntropyLoss(ignore_index=255) as semi_loss and model_D.input_pts
-    equal to the clouds' points, every iteration whose two batches have the
-    same shape is one SegAdvTrainStep (semi=True from iteration semi_start + 1);
-    anything else, and a ragged batch, runs the reference's body through
-    autograd over the same modules.  Checkpoints: epoch_{}, best_cat_iou and
-    best_all_iou (the reference saves none by accuracy here)."""
+def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetloader_nogt_iter,
+                  testloader, testdataset, model, model_D, gan_loss, seg_loss, optimizer,
+                  optimizer_D, history_pool_gt, history_pool_nogt, train_logger, test_logger,
+                  writer, args, semi_loss=None):
+    """The iteration loop shared by run_training_seg (semi_loss None) and
+    run_training_seg_semi (pseudo-label term from iteration semi_start + 1).
+    With PointNetSeg + PointwiseDiscNet, two plain Adams, CrossEntropyLoss +
+    BCEWithLogitsLoss and ImagePool(0) on the HIP device, every iteration whose
+    two batches have the same shape is one SegAdvTrainStep; any other
+    configuration, and a ragged last batch, runs the reference's body through
+    autograd over the same modules.  Where the two reference loops differ, so
+    do these: the fused step's condition, the log line, and the checkpoint by
+    accuracy that only the plain loop writes."""
     from .seg import SegAdvTrainStep
+    with_semi = semi_loss is not None
     max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
     max_train_epoch = max_train_cat_epoch = max_train_all_epoch = 0
     fusable = _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                               history_pool_gt, history_pool_nogt, args) and _semi_fusable(semi_loss)
+                               history_pool_gt, history_pool_nogt, args) \
+        and (not with_semi or _semi_fusable(semi_loss))
+    semi_args = dict(lambda_semi=float(getattr(args, "lambda_semi", 1.0)),
+                     semi_th=float(getattr(args, "semi_TH", 0.8))) if with_semi else {}
     step, eager_since = None, False
     tb = getattr(args, "tensorboard", False) and writer is not None
+    if with_semi:
+        line = ('iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} loss semi = {4:.3f} '
+                'loss_D = {5:.3f}')
+    else:
+        line = 'iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} loss_D = {4:.3f} '
 
     def save(tag):
         if step is not None:
@@ -1438,37 +1283,36 @@ def run_training_seg_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
         batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
         pts_nogt, cls_nogt = batch
         pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
-        semi = args.semi_start > 0 and i_iter > args.semi_start
-        if fusable and pts.shape == pts_nogt.shape and model_D.input_pts == pts.shape[1]:
+        semi = with_semi and args.semi_start > 0 and i_iter > args.semi_start
+        # D's rows are input_pts points each: any whole number of them, but the
+        # semi loop's mask indexes (B, N), as the reference's does
+        if fusable and pts.shape == pts_nogt.shape and (
+                model_D.input_pts == pts.shape[1] if with_semi
+                else (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0):
             if step is None:
                 step = SegAdvTrainStep(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
                                        lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
                                        device=args.device, seed=int(getattr(args, "seed", 0) or 0),
-                                       lambda_semi=float(getattr(args, "lambda_semi", 1.0)),
-                                       semi_th=float(getattr(args, "semi_TH", 0.8)))
+                                       **semi_args)
             elif eager_since:
                 step.after_eager()
             eager_since = False
             step.sync_hyper()
             step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
                  cls_nogt.contiguous(), semi=semi)
-            vals = step.losses_semi.tolist()
+            vals = (step.losses_semi if with_semi else step.losses).tolist()
         else:
             if step is not None:
                 step.sync_optimizer_state()
             eager_since = True
-            vals = _seg_semi_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                                  semi_loss, history_pool_gt, history_pool_nogt, pts, cls, seg,
-                                  pts_nogt, cls_nogt, semi, args)
-        train_logger.info('iter = {0:8d}/{1:8d} '
-                          'loss_seg = {2:.3f} '
-                          'loss_adv = {3:.3f} '
-                          'loss semi = {4:.3f} '
-                          'loss_D = {5:.3f}'.format(i_iter, args.total_iterations, *vals))
+            vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                                 history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
+                                 cls_nogt, args, semi_loss=semi_loss, semi=semi)
+        train_logger.info(line.format(i_iter, args.total_iterations, *vals))
         if tb:
             writer.add_scalar('Loss/train_seg', vals[0], i_iter)
             writer.add_scalar('Loss/train_adv', vals[1], i_iter)
-            writer.add_scalar('Loss/train_disc', vals[3], i_iter)
+            writer.add_scalar('Loss/train_disc', vals[-1], i_iter)
         if i_iter % args.iter_test_epoch == 0:
             ep = i_iter // args.iter_test_epoch
             save("epoch_{}".format(ep))
@@ -1477,6 +1321,8 @@ def run_training_seg_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
                 logger=test_logger, test_iter=i_iter, writer=writer, args=args)
             if max_seg_accu < accu:
                 max_seg_accu, max_train_epoch = accu, ep
+                if not with_semi:  # the reference's semi loop saves none by accuracy
+                    save("best")
             if max_test_cat_iou < cat_iou:
                 max_test_cat_iou, max_train_cat_epoch = cat_iou, ep
                 save("best_cat_iou")
@@ -1492,3 +1338,33 @@ def run_training_seg_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
     if tb:
         writer.close()
     return max_seg_accu, max_test_cat_iou, max_test_all_iou
+
+
+def run_training_seg(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetloader_nogt_iter,
+                     testloader, testdataset, model, model_D, gan_loss, seg_loss, optimizer,
+                     optimizer_D, history_pool_gt, history_pool_nogt, train_logger, test_logger,
+                     writer, args):
+    """utils/trainer.py:849-1026: adversarial segmentation with the per-point
+    discriminator (_seg_adv_loop).  Checkpoints: epoch_{}, best, best_cat_iou
+    and best_all_iou."""
+    return _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                         targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
+                         seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
+                         train_logger, test_logger, writer, args)
+
+
+def run_training_seg_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                          targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
+                          seg_loss, semi_loss, optimizer, optimizer_D, history_pool_gt,
+                          history_pool_nogt, train_logger, test_logger, writer, args):
+    """utils/trainer.py:1903-2121: run_training_seg plus, for i_iter >
+    args.semi_start (> 0), lambda_semi x semi_loss(pred_nogt, argmax(pred_nogt))
+    over the no-GT points the frozen discriminator scores above args.semi_TH
+    (the rest are ignore_index 255).  The fused step (semi=True from iteration
+    semi_start + 1) also needs CrossEntropyLoss(ignore_index=255) as semi_loss
+    and model_D.input_pts equal to the clouds' points.  Checkpoints: epoch_{},
+    best_cat_iou and best_all_iou (the reference saves none by accuracy here)."""
+    return _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                         targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
+                         seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
+                         train_logger, test_logger, writer, args, semi_loss=semi_loss)

@@ -125,7 +125,8 @@ def _worker(rank, port, out_dir):
             m, d = _models(dev)
             st = AdvTrainStep(m, d, B, N, seed=7 + rank, device=dev)
             dp = DataParallelAdvStep(st, overlap=overlap)
-            graph = dp.capture(*_batch(dev, 40 + rank))
+            static = _batch(dev, 40 + rank)  # kept: the graphs read these buffers on every replay
+            graph = dp.capture(*static)
             for k in range(2):
                 dp(*_batch(dev, 20 + 2 * k + rank))   # eager
                 graph.replay()                        # captured halves around the all-reduce

@@ -128,10 +128,10 @@ def test_step_vs_autograd_body(B, N, monkeypatch):
     _replay_labels(monkeypatch, soft)
     args = argparse.Namespace(device=DEV, lambda_seg=lam_seg, lambda_adv=lam_adv,
                               lambda_semi=lam_semi, semi_TH=th)
-    ref = trainer._seg_semi_body(m2, d2, mk(m2), mk(d2), torch.nn.BCEWithLogitsLoss(),
-                                 torch.nn.CrossEntropyLoss(),
-                                 torch.nn.CrossEntropyLoss(ignore_index=255), ImagePool(0),
-                                 ImagePool(0), pts, cls, seg, pts_ng, cls_ng, True, args)
+    ref = trainer._seg_adv_body(m2, d2, mk(m2), mk(d2), torch.nn.BCEWithLogitsLoss(),
+                                torch.nn.CrossEntropyLoss(), ImagePool(0), ImagePool(0), pts, cls,
+                                seg, pts_ng, cls_ng, args,
+                                semi_loss=torch.nn.CrossEntropyLoss(ignore_index=255), semi=True)
     K = int((d_out > th).sum())
     print("fused", losses, "autograd", ref, "kept", int(step.kept.item()), "of", B * N)
     assert int(step.kept.item()) == K and 0 < K < B * N
@@ -338,9 +338,9 @@ def test_run_training_seg_semi_ragged_batch(tmp_path, monkeypatch):
     m, d = _gained(83, 84, N)
     # threshold 0: every point with a positive D output is kept, wherever training moves them
     from adversarial_learning_on_pointclouds_amd import trainer
-    body, eager = trainer._seg_semi_body, []
-    monkeypatch.setattr(trainer, "_seg_semi_body",
-                        lambda *a: eager.append((a[9].shape[0], a[14])) or body(*a))
+    body, eager = trainer._seg_adv_body, []
+    monkeypatch.setattr(trainer, "_seg_adv_body",
+                        lambda *a, **k: eager.append((a[8].shape[0], k["semi"])) or body(*a, **k))
     log, _ = _run_trainer(tmp_path, m, d, torch.optim.Adam,
                           torch.nn.CrossEntropyLoss(ignore_index=255), gt, ng, 5, 0.0, "ragged")
     assert eager == [(1, True)]  # the one-cloud GT batch of iteration 3, with the term on
