@@ -42,8 +42,7 @@ stamps: $(SRC) $(HDR)
 	$(HIPCC) $(HIPFLAGS) -DPCADV_STAMPS -shared -o $(STAMPS_LIB) $(SRC) $(CPP) -lz
 .PHONY: stamps
 
-# A/B variant library (tools/gpu_ab.sh): the same sources with ABDEFS, e.g.
-#   make ab ABDEFS=-DPCADV_K2_PRIO=0
+# A/B variant library (tools/gpu_ab.sh): the same sources with ABDEFS
 ABDEFS ?=
 ab: $(SRC) $(HDR)
 	@mkdir -p build/ab

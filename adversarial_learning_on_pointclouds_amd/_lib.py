@@ -17,7 +17,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PCADV_LIB", os.path.join(_HERE, "lib", "libpcadv.so"))
 # the layout of include/pcadv.h these signatures and AdvArgs bind (pcadv_abi_version())
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 PCADV_OK = 0
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
@@ -176,9 +176,6 @@ SIGNATURES = {
     "pcadv_gemm_bf2": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _i,
                             _vp, _vp, _i, _i, _i, _vp, _i64, _vp]),
     "pcadv_split_bf2": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i64, _vp]),
-    "pcadv_split_bf3": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i64, _vp]),
-    "pcadv_gemm_b3": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i,
-                           _i, _vp]),
     "pcadv_conv_max_bf2": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i,
                                 _vp, _vp, _vp, _sz, _vp]),
     "pcadv_gemm_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -6,10 +6,6 @@
 
 #include "common.h"
 
-#ifndef PCADV_CLS_PRESORT
-#define PCADV_CLS_PRESORT 1  // A/B builds: 0 = the cls step's chunks sort their own hits
-#endif
-
 namespace pcadv {
 
 static thread_local char g_err[512] = "";
@@ -75,9 +71,6 @@ int launch_disc_tail(const float*, int, const float*, const float*, const float*
                      const int32_t* gidx, int C, int N, int* sortrec, float* z4g, float* z5g,
                      float* a4g, int lab_off = 0);
 size_t feat_sort_record_ints(int C, int N);
-#if defined(PCADV_C4_CERT) && PCADV_C4_CERT
-int c4_cert_read(unsigned* host);
-#endif
 #ifdef PCADV_STAMPS
 int tail_stamps_read(uint64_t* host);
 int chunk_stamps_read(uint64_t* host);
@@ -94,9 +87,6 @@ int launch_gemm_bf2(const void*, const void*, long long, const void*, const void
                     long long, void*, void*, long long, int, int, int, const float*, const float*,
                     int, int, int, const float*, long long, hipStream_t);
 int launch_split_bf2(const float*, long long, int, int, void*, void*, long long, hipStream_t);
-int launch_split_bf3(const float*, long long, int, int, void*, void*, void*, long long, hipStream_t);
-int launch_gemm_b3(const float*, long long, const void*, const void*, const void*, long long, float*,
-                   long long, int, int, int, const float*, const float*, int, int, int, hipStream_t);
 size_t gemm_wgrad_workspace_bytes(int, int, int, int);
 int launch_gemm_wgrad(const float*, long long, const float*, long long, int, int, int, float*,
                       long long, float*, float*, int, int, void*, size_t, hipStream_t);
@@ -205,23 +195,12 @@ static StepWs carve(int B, int N, char* base) {
 // Adam fused into the feature backward's finishing launch (apply_adam): G's
 // conv1..conv4 as their gradients are formed there, the rest of G and all of D
 // in extra blocks of the same launch (their gradients are final by then).
-// The fused Adam of a whole step is split by where each gradient becomes
-// final: fc2, fc3 and all of D before fc1's backward launch (their update rides
-// along it: early = true), fc1 before the chunk launch (its trailing
-// workgroups), conv1..conv4 in the finishing launch.
-#ifndef PCADV_EARLY_ADAM
-#define PCADV_EARLY_ADAM 0  // A/B builds: 1 = fc2, fc3 and D ride along fc1's backward (measured slower)
-#endif
-// whole: the chunk launch's share when no fc1 backward ran in this call (part 2)
-static FinAdam fused_adam(const pcadv_adv_args* a, bool with_d, bool early = false,
-                          bool whole = false) {
-  const bool split = PCADV_EARLY_ADAM && !whole;
+static FinAdam fused_adam(const pcadv_adv_args* a, bool with_d) {
   FinAdam f{};
   f.on = 1;
   f.gp = a->g_param; f.gm = a->g_m; f.gv = a->g_v; f.gg = a->g_grad;
-  f.g_rest0 = split && early ? PCADV_G_FC2_W : PCADV_G_FC1_W;
-  f.g_n = split && !early ? PCADV_G_FC2_W : PCADV_G_NUMEL;
-  with_d = with_d && (!split || early);
+  f.g_rest0 = PCADV_G_FC1_W;
+  f.g_n = PCADV_G_NUMEL;
   if (with_d) {
     f.dp = a->d_param; f.dm = a->d_m; f.dv = a->d_v; f.dg = a->d_grad;
     f.d_n = PCADV_D_NUMEL;
@@ -304,7 +283,7 @@ static int adv_step(const pcadv_adv_args* a, hipStream_t s) {
   //      optimizer_D.step() (:558-559) fused into its finishing launch --------
   PC_REQUIRE(!a->apply_adam || (a->g_m && a->g_v && a->d_param && a->d_m && a->d_v),
              "adv_step: Adam buffers");
-  const FinAdam fa = fused_adam(a, true, false, a->part == 2);
+  const FinAdam fa = fused_adam(a, true);
   IterEpi epi;
   bool epi_on;
   PC_TRY(step_epilogue(a, &epi, &epi_on));
@@ -442,13 +421,7 @@ static int adv_head_part(const pcadv_adv_args* a, hipStream_t s, const StepWs& w
                              C, 256, 512, s, &ex));
   }
   {
-    // fc2, fc3 and D are final: their Adam (optimizer.step / optimizer_D.step,
-    // :558-559) rides along fc1's backward
     LinBwdExtra ex{};
-    if (a->apply_adam && PCADV_EARLY_ADAM) {
-      PC_REQUIRE(a->g_m && a->g_v && a->d_param && a->d_m && a->d_v, "adv_step: Adam buffers");
-      ex.adam = fused_adam(a, true, true);
-    }
     PC_TRY(launch_linear_bwd(w.dh1, nullptr, PCADV_ACT_NONE, nullptr, nullptr, 0, 0.f, gmax,
                              G + PCADV_G_FC1_W, dgmax, gG + PCADV_G_FC1_W, gG + PCADV_G_FC1_B, C,
                              C, 512, 1024, s, &ex));
@@ -515,7 +488,7 @@ static int cls_step(const pcadv_adv_args* a, hipStream_t s) {
   // and fc3's input gradient, stored as fc2's dz (k_cls_head)
   PC_TRY(launch_cls_head(w.h2, w.mask, a->drop_p, G + PCADV_G_FC3_W, G + PCADV_G_FC3_B, a->labels,
                          B, a->lambda_cls, logits, w.dlogits, w.dh2, w.rowloss, s,
-                         ext ? nullptr : w.gidx, C, N, ext || !PCADV_CLS_PRESORT ? nullptr : w.sortrec));
+                         ext ? nullptr : w.gidx, C, N, ext ? nullptr : w.sortrec));
   {
     // fc2's backward; fc3's weight gradient and the CE batch mean ride along
     LinBwdExtra ex{};
@@ -532,11 +505,7 @@ static int cls_step(const pcadv_adv_args* a, hipStream_t s) {
                              C, 256, 512, s, &ex));
   }
   {
-    LinBwdExtra ex{};  // fc2 and fc3 are final: their Adam rides along fc1's backward
-    if (a->apply_adam && !ext && PCADV_EARLY_ADAM) {
-      PC_REQUIRE(a->g_m && a->g_v, "cls_step: Adam moments");
-      ex.adam = fused_adam(a, false, true);
-    }
+    LinBwdExtra ex{};
     PC_TRY(launch_linear_bwd(w.dh1, nullptr, PCADV_ACT_NONE, nullptr, nullptr, 0, 0.f, gmax,
                              G + PCADV_G_FC1_W, dgmax, gG + PCADV_G_FC1_W, gG + PCADV_G_FC1_B, C,
                              C, 512, 1024, s, &ex));
@@ -555,7 +524,7 @@ static int cls_step(const pcadv_adv_args* a, hipStream_t s) {
                          gG + PCADV_G_CONV2_B, gG + PCADV_G_CONV3_W, gG + PCADV_G_CONV3_B,
                          gG + PCADV_G_CONV4_W, gG + PCADV_G_CONV4_B, w.feat_ws, w.feat_ws_bytes,
                          s, nullptr, a->apply_adam ? &fa : nullptr,
-                         PCADV_CLS_PRESORT ? w.sortrec : nullptr, epi_on ? &epi : nullptr,
+                         w.sortrec, epi_on ? &epi : nullptr,
                          a->precision == 1);
 }
 
@@ -566,7 +535,7 @@ using namespace pcadv;
 extern "C" {
 
 const char* pcadv_last_error(void) { return g_err; }
-int pcadv_abi_version(void) { return 10; }
+int pcadv_abi_version(void) { return 11; }
 
 size_t pcadv_feat_fwd_workspace_bytes(int C, int N) { return feat_fwd_workspace_bytes(C, N); }
 
@@ -608,12 +577,6 @@ int pcadv_feat_fwd_stamped(const float* pts, int C, int N, const float* w1, cons
 
 size_t pcadv_feat_bwd_workspace_bytes(int C, int N) { return feat_bwd_workspace_bytes(C, N); }
 
-#if defined(PCADV_C4_CERT) && PCADV_C4_CERT
-// diagnostic build only (tools/cert_diag.py): k_conv4_max's certification
-// counters since the last read: [flagged at the rigorous bound, channels,
-// flagged at 2^-17 x the bound, launches]
-int pcadv_c4_cert_read(unsigned* host) { return c4_cert_read(host); }
-#endif
 #ifdef PCADV_STAMPS
 int pcadv_tail_stamps(uint64_t* host) { return tail_stamps_read(host); }
 int pcadv_chunk_stamps(uint64_t* host) { return chunk_stamps_read(host); }
@@ -768,19 +731,6 @@ int pcadv_gemm_bf2(const void* a_hi, const void* a_lo, int64_t lda, const void* 
 int pcadv_split_bf2(const float* x, int64_t ld, int rows, int cols, void* hi, void* lo,
                     int64_t ldo, hipStream_t stream) {
   return launch_split_bf2(x, ld, rows, cols, hi, lo, ldo, stream);
-}
-
-int pcadv_split_bf3(const float* x, int64_t ld, int rows, int cols, void* hi, void* mid, void* lo,
-                    int64_t ldo, hipStream_t stream) {
-  return launch_split_bf3(x, ld, rows, cols, hi, mid, lo, ldo, stream);
-}
-
-int pcadv_gemm_b3(const float* a, int64_t lda, const void* b_hi, const void* b_mid,
-                  const void* b_lo, int64_t ldb, float* c, int64_t ldc, int M, int N, int K,
-                  const float* bias, const float* bias_rows, int rows_per_group, int relu,
-                  int accumulate, hipStream_t stream) {
-  return launch_gemm_b3(a, lda, b_hi, b_mid, b_lo, ldb, c, ldc, M, N, K, bias, bias_rows,
-                        rows_per_group, relu, accumulate, stream);
 }
 
 size_t pcadv_gemm_wgrad_workspace_bytes(int rows, int O, int Kin, int rows_per_group) {

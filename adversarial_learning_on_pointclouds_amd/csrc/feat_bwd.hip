@@ -72,13 +72,7 @@ static_assert(FS_PCH == BW_PCH && FS_MAXO == BW_MAXO && FS_T == BW_T, "feat_sort
 // backward: the generator from fc1 on (segment 0) and the discriminator
 // (segment 1), in trailing workgroups of k_feat_bwd_chunk (NT = BW_T threads);
 // V4 float4 per thread and pass, blocks [0, nb0) on segment 0.
-#ifndef PCADV_FIN_ADAM_V4
-#define PCADV_FIN_ADAM_V4 4
-#endif
-#ifndef PCADV_TRAIL_ADAM_FIRST
-#define PCADV_TRAIL_ADAM_FIRST 0
-#endif
-constexpr int FIN_ADAM_V4 = PCADV_FIN_ADAM_V4;  // float4 per thread in the chunk launch's Adam workgroups
+constexpr int FIN_ADAM_V4 = 4;  // float4 per thread in the chunk launch's Adam workgroups
 template <int NT, int V4>
 __device__ void adam_range(int b, int nb, float* p, float* m, float* v, const float* g, int64_t n,
                            float lr, const FinAdam& fa) {
@@ -240,10 +234,10 @@ k_feat_bwd_chunk(const float* __restrict__ dg, const int32_t* __restrict__ gidx,
     const int b = ((int)blockIdx.y - nclouds) * (int)gridDim.x + (int)blockIdx.x;
     constexpr int NDW4 = BW_MAXO / (BW_T / 64 / DW4_WPC);
     const int nad = nb_adam0 + nb_adam1;
-    const bool is_dw4 = PCADV_TRAIL_ADAM_FIRST ? (b >= nad && b - nad < NDW4) : b < NDW4;
-    const int bd = PCADV_TRAIL_ADAM_FIRST ? b - nad : b, ba = PCADV_TRAIL_ADAM_FIRST ? b : b - NDW4;
+    const bool is_dw4 = b < NDW4;  // the dW4 gather's blocks come first
+    const int ba = b - NDW4;
     if (is_dw4)
-      dw4_block<BW_T / 64, XB>(bd, reinterpret_cast<float4(*)[64]>(smem), dg, gidx, nclouds, N, O, x3,
+      dw4_block<BW_T / 64, XB>(b, reinterpret_cast<float4(*)[64]>(smem), dg, gidx, nclouds, N, O, x3,
                            dw4, db4);
     else if (ba >= 0 && ba < nad)
       adam_block<BW_T, FIN_ADAM_V4>(ba, nb_adam0, nb_adam1, fa);
@@ -816,10 +810,7 @@ __device__ void reduce_slabs_block(int blk, float (*part)[64], const float* __re
 // chunks read W4 until they end).  The dW4 gather and the other Adam work rode
 // along k_feat_bwd_chunk.
 constexpr int FIN_NRED = (SLAB + FIN_COLS - 1) / FIN_COLS;
-#ifndef PCADV_FIN_W4_SPREAD
-#define PCADV_FIN_W4_SPREAD 1  // A/B builds: 0 = conv4's Adam on the fewest blocks (two float4 per thread)
-#endif
-constexpr int FIN_W4_V4 = PCADV_FIN_W4_SPREAD ? 1 : 2;
+constexpr int FIN_W4_V4 = 1;  // conv4's Adam spread over the CUs the reduction leaves free
 constexpr int FIN_CUS = 256;  // MI355X compute units
 __global__ void __launch_bounds__(1024)
 k_feat_bwd_finish(const float* __restrict__ slabs, int nslabs, float* dw1, float* db1, float* dw2,
@@ -902,7 +893,7 @@ int launch_feat_bwd(const float* dg, const int32_t* gidx, const float* pts_a, co
   int nb4 = 0;
   if (fa.on) {
     nb4 = fin_adam_blocks(PCADV_G_CONV4_B + PCADV_C4 - PCADV_G_CONV4_W, 1024, FIN_W4_V4);
-    if (PCADV_FIN_W4_SPREAD && nb4 < FIN_CUS - FIN_NRED) nb4 = FIN_CUS - FIN_NRED;
+    if (nb4 < FIN_CUS - FIN_NRED) nb4 = FIN_CUS - FIN_NRED;
   }
   hipLaunchKernelGGL(k_feat_bwd_finish, dim3(FIN_NRED + nb4), dim3(1024), 0, s, slabs, C * nchunk,
                      dw1, db1, dw2, db2, dw3, db3, fa, nb4, epi ? *epi : IterEpi{});

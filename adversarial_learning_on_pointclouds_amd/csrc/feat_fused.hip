@@ -40,6 +40,7 @@ __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
 // ============================================================================
 constexpr int PM_P = 64;    // points per tile
 constexpr int PM_T = 256;   // 4 waves; 2 workgroups per CU (register-bound)
+constexpr int PM_ONE_BELOW = 1024;  // the tile count below which one tile per workgroup runs
 // TPW: tiles per workgroup (the next tile's points are prefetched): 2, or 1 when
 // two would leave fewer than two workgroups per CU (fewer than 64 clouds at N = 1024)
 constexpr int X2S = 72;     // bf16 row stride of the x2 planes (144 B: conflict-free b128 reads)
@@ -355,26 +356,11 @@ k_point_mlp(const float* __restrict__ pts_a, const float* __restrict__ pts_b, in
 // ============================================================================
 // k_conv4_max: conv4 (128 -> 1024) + max over points
 // ============================================================================
-#ifndef PCADV_C4_CERT
-// diagnostic builds only (make ab ABDEFS=-DPCADV_C4_CERT=1): every lane also
-// tracks the largest screened key it DROPS (the channel's third candidate),
-// and after the exact re-evaluation a channel is counted when that third value
-// plus a rigorous screening-error bound reaches the winner's exact value -
-// what certifying the argmax would have to re-check (tools/cert_diag.py)
-#define PCADV_C4_CERT 0
-#endif
-#if PCADV_C4_CERT
-// [0] channels counted, [1] channels seen, [2] channels whose third screened
-// value lies within 2^-16 x the bound (an empirical band), [3] launches
-__device__ unsigned int g_c4_cert[4];
-#endif
-#ifndef PCADV_C4_DIAG
-#define PCADV_C4_DIAG 0  // diagnostic builds only: 1 = no screening, 2 = no staging
-#endif
 constexpr int C4_O = 1024;  // conv4 output channels
 constexpr int C4_CB = 256;  // channels per workgroup (8 waves x 32)
 constexpr int C4_T = 512;
 constexpr int C4_P = 64;    // points per step
+constexpr int C4_G2_MAXC = 63;  // the largest cloud count run in the two-group (G2) form
 constexpr int C4_SB = 136;  // bf16 row stride of the x3 hi / lo tiles (272 B: conflict-free b128 reads)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -406,11 +392,6 @@ __device__ __forceinline__ int screen_key(float v, int lowc) {
 template <int LOWC>
 __device__ __forceinline__ int screen_key_asm(float v, int m_ord, int m_hi) {
   int t;
-#if PCADV_C4_DIAG & 4  // diagnostic builds only: one instruction, order wrong for negative values
-  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xea" : "=&v"(t) : "v"(v), "s"(m_hi), "n"(LOWC));
-  (void)m_ord;
-  return t;
-#endif
   asm("v_ashrrev_i32 %0, 31, %1\n\t"
       "v_bitop3_b32 %0, %1, %0, %2 bitop3:0x78\n\t"
       "v_bitop3_b32 %0, %0, %3, %4 bitop3:0xea"
@@ -422,16 +403,15 @@ __device__ __forceinline__ int screen_key_asm(float v, int m_ord, int m_hi) {
 // top-2 (TOP2) or top-1 (bf16 mode, whose result is the screened winner itself)
 template <int I, bool TOP2>
 __device__ __forceinline__ void screen_one(const f32x16& acc, int m_ord, int m_hi, int& k1,
-                                           int& k2, int& k3) {
+                                           int& k2) {
   const int key = screen_key_asm<31 - ((I & 3) + 8 * (I >> 2))>(acc[I], m_ord, m_hi);
-  if constexpr (PCADV_C4_CERT && TOP2) k3 = max(min(key, k2), k3);  // the key k2 / key drops
   if constexpr (TOP2) k2 = max(min(key, k1), k2);  // median(key, k1, k2) for k2 <= k1: v_med3_i32
   k1 = max(k1, key);
 }
 template <int I0, bool TOP2, int... J>
 __device__ __forceinline__ void screen_seq(const f32x16& acc, int m_ord, int m_hi, int& k1,
-                                           int& k2, int& k3, std::integer_sequence<int, J...>) {
-  (screen_one<I0 + J, TOP2>(acc, m_ord, m_hi, k1, k2, k3), ...);
+                                           int& k2, std::integer_sequence<int, J...>) {
+  (screen_one<I0 + J, TOP2>(acc, m_ord, m_hi, k1, k2), ...);
 }
 __device__ __forceinline__ int key_row(int k) { return 31 - (k & 63); }
 __device__ __forceinline__ float key_value(int k) {
@@ -512,19 +492,13 @@ __device__ __forceinline__ void pair_merge(int n1, int u1, int n2, int u2, int& 
 // 128-point steps, units 4 s + grp): the bf16 staging fits twice the rows in
 // the same LDS, W4 needs no lo fragments, and half as many step barriers are
 // shared by twice the waves.
-#ifndef PCADV_C4_G4
-#define PCADV_C4_G4 1  // A/B builds: 0 = XB workgroups keep two wave groups
-#endif
 template <int NP4, bool G2, bool XB>
-constexpr int c4_groups() { return G2 ? (XB && PCADV_C4_G4 ? 4 : 2) : 1; }
+constexpr int c4_groups() { return G2 ? (XB ? 4 : 2) : 1; }
 template <int NP4, bool G2, bool XB>
 constexpr int c4_threads() { return c4_groups<NP4, G2, XB>() == 4 ? 2 * C4_T : C4_T; }
 
 // P128 (the 256-channel form, N % 128 == 0): 128-point steps, four units per
 // wave and step, two staged rows per thread: half the step barriers.
-#ifndef PCADV_C4_P128
-#define PCADV_C4_P128 1  // A/B builds: 0 = 64-point steps throughout
-#endif
 template <int NP4, bool G2, bool XB = false, bool P128 = false>
 __global__ void __launch_bounds__((c4_threads<NP4, G2, XB>()))
 k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict__ w4,
@@ -582,13 +556,6 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
       }
     }
   };
-  float cert_ss = 0.f, cert_xn2 = 0.f;  // PCADV_C4_CERT >= 2: max_p ||x_p||^2 of the cloud
-  auto cert_row_done = [&]() {
-    if constexpr (PCADV_C4_CERT >= 2) {
-      cert_xn2 = fmaxf(cert_xn2, octet_sum(cert_ss));
-      cert_ss = 0.f;
-    }
-  };
   auto stage_write = [&](int buf) {  // split the staged f32 rows into bf16 hi / lo
 #pragma unroll
     for (int q = 0; q < RPT; ++q) {
@@ -603,7 +570,6 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const float v = stg[4 * q + (j >> 2)][j & 3];
-        if constexpr (PCADV_C4_CERT >= 2) cert_ss = fmaf(v, v, cert_ss);
         const __bf16 hb = (__bf16)v;
         hi[j >> 3][j & 7] = hb;
         lo[j >> 3][j & 7] = (__bf16)(v - (float)hb);
@@ -657,7 +623,6 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
   }
   __syncthreads();  // every wave holds its fragments before tile 0 overwrites the staging rows
   stage_write(0);
-  cert_row_done();
   stage_load(1);
   __syncthreads();
   STAMP(1);
@@ -668,32 +633,22 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
   // lane's own h (keys are only compared within a lane).
   int r1 = KEY_NONE, r2 = KEY_NONE;
   int t1 = -1, t2 = -1;
-  int r3 = KEY_NONE;  // PCADV_C4_CERT: the largest truncated key this lane dropped
   auto screen_unit = [&](const f32x16& acc, int u, auto MASKED, int kb_lo, int kb_hi, int& k1,
-                         int& k2, int& k3) {
+                         int& k2) {
 #pragma unroll
     for (int i = 2 * kb_lo; i < 2 * kb_hi; ++i) {
       if constexpr (decltype(MASKED)::value)
         if (u * 32 + acc_row(i, lane) >= N) continue;
       const int key = screen_key(acc[i], 31 - acc_row(i, 0));
-      if constexpr (PCADV_C4_CERT && NP4 == 3) k3 = max(min(key, k2), k3);
       if constexpr (NP4 == 3) k2 = max(min(key, k1), k2);  // median(key, k1, k2): v_med3_i32
       k1 = max(k1, key);
     }
   };
   // unmasked screening of acc elements [I, I + CNT) with the asm keys
   const int m_ord = 0x7fffffc0, m_hi = ~63;
-  auto screen_fast = [&](const f32x16& acc, auto I, auto CNT, int& k1, int& k2, int& k3) {
-    screen_seq<decltype(I)::value, NP4 == 3>(acc, m_ord, m_hi, k1, k2, k3,
+  auto screen_fast = [&](const f32x16& acc, auto I, auto CNT, int& k1, int& k2) {
+    screen_seq<decltype(I)::value, NP4 == 3>(acc, m_ord, m_hi, k1, k2,
                                              std::make_integer_sequence<int, decltype(CNT)::value>{});
-  };
-  // PCADV_C4_CERT: a unit's top-2 (n1 >= n2) and dropped max n3 merged into the
-  // running r1, r2, r3: the third largest of {n1, n2, r1, r2} is dropped too
-  auto cert_merge = [&](int n1, int n2, int n3) {
-    if constexpr (PCADV_C4_CERT && NP4 == 3) {
-      const int m1 = n1 & ~63, m2 = n2 & ~63, q1 = r1 & ~63, q2 = r2 & ~63;
-      r3 = max(r3, max(n3 & ~63, max(min(m1, q2), min(m2, q1))));
-    }
   };
 
   // Software pipeline over 32-point units (step s, half pt): the 24 MFMAs of a
@@ -709,7 +664,7 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
     // this unit's share of the staging: row q = pt of the thread's rows (G2: its one row)
     const bool stg_turn = G2 || pt < RPT;
     const int q = G2 ? 0 : (pt < RPT ? pt : 0);
-    int k1 = KEY_NONE, k2 = KEY_NONE, k3 = KEY_NONE;
+    int k1 = KEY_NONE, k2 = KEY_NONE;
     bf16x8 fa[3][2];  // A fragments, a 3-deep register ring: [k-block % 3][hi, lo]
     auto frag = [&](int kb) {
       fa[kb % 3][0] = *reinterpret_cast<const bf16x8*>(xh + 16 * kb);
@@ -731,50 +686,48 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
       }
       cur = mfma_bf16(ah, bh[kb], cur);
       if constexpr (decltype(SCREEN)::value && decltype(MASKED)::value) {
-        screen_unit(prev, uprev, MASKED, kb, kb + 1, k1, k2, k3);
+        screen_unit(prev, uprev, MASKED, kb, kb + 1, k1, k2);
         asm volatile("" ::"v"(k1), "v"(k2));
-      } else if constexpr (decltype(SCREEN)::value && !(PCADV_C4_DIAG & 1)) {
+      } else if constexpr (decltype(SCREEN)::value) {
         // 16 values over k-blocks 1..7 (2,2,2,2,2,3,3); none in k-block 0, so the
         // previous unit's MFMAs have retired before the asm reads them
         // (tools/check_asm_hazards.py checks the distance in the ISA)
         using IC = std::integral_constant<int, 0>;
         if constexpr (NP4 == 3 || !P128) {
-          if (kb == 1) screen_fast(prev, IC{}, std::integral_constant<int, 2>{}, k1, k2, k3);
-          if (kb == 2) screen_fast(prev, std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, k1, k2, k3);
-          if (kb == 3) screen_fast(prev, std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{}, k1, k2, k3);
-          if (kb == 4) screen_fast(prev, std::integral_constant<int, 6>{}, std::integral_constant<int, 2>{}, k1, k2, k3);
-          if (kb == 5) screen_fast(prev, std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{}, k1, k2, k3);
-          if (kb == 6) screen_fast(prev, std::integral_constant<int, 10>{}, std::integral_constant<int, 3>{}, k1, k2, k3);
-          if (kb == 7) screen_fast(prev, std::integral_constant<int, 13>{}, std::integral_constant<int, 3>{}, k1, k2, k3);
+          if (kb == 1) screen_fast(prev, IC{}, std::integral_constant<int, 2>{}, k1, k2);
+          if (kb == 2) screen_fast(prev, std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, k1, k2);
+          if (kb == 3) screen_fast(prev, std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{}, k1, k2);
+          if (kb == 4) screen_fast(prev, std::integral_constant<int, 6>{}, std::integral_constant<int, 2>{}, k1, k2);
+          if (kb == 5) screen_fast(prev, std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{}, k1, k2);
+          if (kb == 6) screen_fast(prev, std::integral_constant<int, 10>{}, std::integral_constant<int, 3>{}, k1, k2);
+          if (kb == 7) screen_fast(prev, std::integral_constant<int, 13>{}, std::integral_constant<int, 3>{}, k1, k2);
         } else {
           // bf16 mode's P128 form: one MFMA per k-block and back-to-back units,
           // so k-blocks 0 and 1 stand between the previous unit's last MFMA
           // and the first read
-          if (kb == 2) screen_fast(prev, IC{}, std::integral_constant<int, 3>{}, k1, k2, k3);
-          if (kb == 3) screen_fast(prev, std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{}, k1, k2, k3);
-          if (kb == 4) screen_fast(prev, std::integral_constant<int, 6>{}, std::integral_constant<int, 3>{}, k1, k2, k3);
-          if (kb == 5) screen_fast(prev, std::integral_constant<int, 9>{}, std::integral_constant<int, 3>{}, k1, k2, k3);
-          if (kb == 6) screen_fast(prev, std::integral_constant<int, 12>{}, std::integral_constant<int, 2>{}, k1, k2, k3);
-          if (kb == 7) screen_fast(prev, std::integral_constant<int, 14>{}, std::integral_constant<int, 2>{}, k1, k2, k3);
+          if (kb == 2) screen_fast(prev, IC{}, std::integral_constant<int, 3>{}, k1, k2);
+          if (kb == 3) screen_fast(prev, std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{}, k1, k2);
+          if (kb == 4) screen_fast(prev, std::integral_constant<int, 6>{}, std::integral_constant<int, 3>{}, k1, k2);
+          if (kb == 5) screen_fast(prev, std::integral_constant<int, 9>{}, std::integral_constant<int, 3>{}, k1, k2);
+          if (kb == 6) screen_fast(prev, std::integral_constant<int, 12>{}, std::integral_constant<int, 2>{}, k1, k2);
+          if (kb == 7) screen_fast(prev, std::integral_constant<int, 14>{}, std::integral_constant<int, 2>{}, k1, k2);
         }
         // pin the keys to this region (otherwise the IR passes sink the whole
         // screening below the MFMAs, next to its only use)
         asm volatile("" ::"v"(k1), "v"(k2));
       }
-      if (!XB && (PCADV_C4_DIAG & 2) == 0 && stg_turn && kb < 4) {  // split the staged f32 rows into bf16 hi / lo, 4 per k-block
+      if (!XB && stg_turn && kb < 4) {  // split the staged f32 rows into bf16 hi / lo, 4 per k-block
 #pragma unroll
         for (int j = 4 * kb; j < 4 * kb + 4; ++j) {
           const float v = stg[4 * q + (j >> 2)][j & 3];
-          if constexpr (PCADV_C4_CERT >= 2) cert_ss = fmaf(v, v, cert_ss);
           const __bf16 hb = (__bf16)v;
           shi[j >> 3][j & 7] = hb;
           if constexpr (NP4 == 3) slo[j >> 3][j & 7] = (__bf16)(v - (float)hb);
         }
-        if (kb == 3) cert_row_done();
         if constexpr (NP4 == 3) asm volatile("" ::"v"(shi[kb >> 1]), "v"(slo[kb >> 1]));
         else asm volatile("" ::"v"(shi[kb >> 1]));
       }
-      if ((PCADV_C4_DIAG & 2) == 0 && stg_turn && kb == 4) {  // the next step's tile (buffer free since the barrier)
+      if (stg_turn && kb == 4) {  // the next step's tile (buffer free since the barrier)
         bf16x8* dh = reinterpret_cast<bf16x8*>(&L.x[buf ^ 1][0][(srow + 64 * q) * C4_SB + sk]);
         bf16x8* dl = reinterpret_cast<bf16x8*>(&L.x[buf ^ 1][1][(srow + 64 * q) * C4_SB + sk]);
         dh[0] = XB ? stgb[2 * q] : shi[0];
@@ -786,11 +739,10 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
       }
       // tile s + 2 into the staging registers just freed (clamped: past the
       // end it re-reads the last row): 1.5 units ahead of its conversion
-      if ((PCADV_C4_DIAG & 2) == 0 && (G2 || pt == RPT - 1) && kb == 4) stage_load(s + 2);
+      if ((G2 || pt == RPT - 1) && kb == 4) stage_load(s + 2);
     }
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (decltype(SCREEN)::value) {
-      cert_merge(k1, k2, k3);
       pair_merge<NP4 == 3>(k1, uprev, k2, uprev, r1, t1, r2, t2);
     }
   };
@@ -850,39 +802,21 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
         wv[G][u] = *reinterpret_cast<const f32x4*>(wbase + (size_t)(8 * G + oc) * 128 + 4 * u);
   }
   if constexpr (G2) {  // this wave's last unit
-    int k1 = KEY_NONE, k2 = KEY_NONE, k3 = KEY_NONE;
+    int k2 = KEY_NONE, k1 = KEY_NONE;
     const int ul = NGRP * (S - 1) + grp;
-    if ((S - 1) & 1) screen_unit(accB, ul, T_{}, 0, 8, k1, k2, k3);
-    else screen_unit(accA, ul, T_{}, 0, 8, k1, k2, k3);
-    cert_merge(k1, k2, k3);
+    if ((S - 1) & 1) screen_unit(accB, ul, T_{}, 0, 8, k1, k2);
+    else screen_unit(accA, ul, T_{}, 0, 8, k1, k2);
     pair_merge<NP4 == 3>(k1, ul, k2, ul, r1, t1, r2, t2);
   } else {  // the last unit
-    int k1 = KEY_NONE, k2 = KEY_NONE, k3 = KEY_NONE;
-    screen_unit(accB, UPS * S - 1, T_{}, 0, 8, k1, k2, k3);
-    cert_merge(k1, k2, k3);
+    int k1 = KEY_NONE, k2 = KEY_NONE;
+    screen_unit(accB, UPS * S - 1, T_{}, 0, 8, k1, k2);
     pair_merge<NP4 == 3>(k1, UPS * S - 1, k2, UPS * S - 1, r1, t1, r2, t2);
   }
   STAMP(2);
 
-#if PCADV_C4_CERT >= 2
-  __shared__ unsigned cert_xn2_wg;  // max over the workgroup's rows (non-negative: uint order)
-  if (tid == 0) cert_xn2_wg = 0u;
-  __syncthreads();
-  atomicMax(&cert_xn2_wg, __float_as_uint(cert_xn2));
-  __syncthreads();
-  const float cert_xn = sqrtf(__uint_as_float(cert_xn2_wg));
-#endif
   // lanes l and l + 32 hold the same channel over interleaved rows
   {
     const int o1 = __shfl_xor(r1, 32), o2 = __shfl_xor(r2, 32);
-    // PCADV_C4_CERT: the channel's third screened value = the largest of both
-    // lanes' dropped keys and the third of the four candidates merged here
-    float cert_v3 = -INFINITY;
-    if constexpr (PCADV_C4_CERT && NP4 == 3) {
-      const int q3 = max(max(r3, __shfl_xor(r3, 32)),
-                         max(min(r1 & ~63, o2 & ~63), min(r2 & ~63, o1 & ~63)));
-      cert_v3 = q3 == KEY_NONE ? -INFINITY : key_value(q3);
-    }
     const int u1 = __shfl_xor(t1, 32), u2 = __shfl_xor(t2, 32);
     // order by (value, global index): decode both pairs first
     const int hm = 4 * h, ho = 4 - hm;  // row offsets of this lane half and the other
@@ -919,20 +853,14 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
       // free: the point loop's last barrier has passed (256 slots per group)
       float* xv = L.w[0] + 256 * (grp > 0 ? grp - 1 : 0);
       int* xi = reinterpret_cast<int*>(L.w[1]) + 256 * (grp > 0 ? grp - 1 : 0);
-      float* x3v = L.w[2];
       if (grp > 0 && h == 0) {
         xv[2 * slot] = v1;
         xv[2 * slot + 1] = v2;
         xi[2 * slot] = a1;
         xi[2 * slot + 1] = a2;
-        if constexpr (PCADV_C4_CERT && NP4 == 3) x3v[slot] = cert_v3;
       }
       __syncthreads();
       if (grp > 0) return;
-      if constexpr (PCADV_C4_CERT && NP4 == 3) {
-        const float g1 = xv[2 * slot], g2 = xv[2 * slot + 1];
-        cert_v3 = fmaxf(fmaxf(cert_v3, x3v[slot]), fmaxf(fminf(v1, g2), fminf(v2, g1)));
-      }
 #pragma unroll
       for (int q = 0; q < 2 * (NGRP - 1); ++q) {  // group 1's pair, then group 2's, ...
         const float v = xv[256 * (q >> 1) + 2 * slot + (q & 1)];
@@ -1022,26 +950,6 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
       gmax[(size_t)c * C4_O + o] = gv;
       gidx[(size_t)c * C4_O + o] = gi;
     }
-#if PCADV_C4_CERT == 1
-    asm volatile("" ::"v"(cert_v3));  // tracking cost only
-#elif PCADV_C4_CERT >= 2
-    {
-      // a dropped point p has exact value <= s_p + err_p <= v3 + err, with the
-      // screening error err <= 2^-14.3 sum_k |x_pk w_ok| (three dropped split
-      // terms <= 3 2^-18, up to 384 f32 accumulation roundings <= 2^-15.4, the
-      // 2^-17 key truncation) <= 2^-14 ||x_p|| ||w_o|| (Cauchy-Schwarz)
-      float wn2 = 0.f;
-      for (int k = 0; k < 128; ++k) wn2 = fmaf(w4[(size_t)o * 128 + k], w4[(size_t)o * 128 + k], wn2);
-      const float bound = cert_xn * sqrtf(wn2);
-      const float ew = second ? res2 : res1;  // the winner's exact value, no bias
-      if (h == 0) {
-        atomicAdd(&g_c4_cert[0], cert_v3 + 0x1p-14f * bound >= ew ? 1u : 0u);
-        atomicAdd(&g_c4_cert[1], 1u);
-        atomicAdd(&g_c4_cert[2], cert_v3 + 0x1p-17f * bound >= ew ? 1u : 0u);
-      }
-      if (blockIdx.x == 0 && tid == 0) atomicAdd(&g_c4_cert[3], 1u);
-    }
-#endif
   }
   STAMP(3);
 #undef STAMP
@@ -1074,12 +982,6 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
 // the 64 banks once, and the staging map below does so for every 8-lane group
 // of its ds_write_b128.
 // ----------------------------------------------------------------------------
-#ifndef PCADV_C4_W16
-// A/B builds: 0 = that case stays with the P128 form (the diagnostic CERT / DIAG
-// builds instrument the forms above only)
-#define PCADV_C4_W16 (PCADV_C4_CERT == 0 && PCADV_C4_DIAG == 0)
-#endif
-#if PCADV_C4_W16
 struct C4W16 {};  // form tag
 constexpr int C4W_T = 1024;
 
@@ -1096,9 +998,6 @@ __device__ __forceinline__ int c4w_slot(int p) {
 // 16-B chunk of a k-block that lane quarter q multiplies (A and B alike)
 __device__ __forceinline__ int c4w_kq(int q) { return ((q & 1) << 1) | (q >> 1); }
 
-#ifndef PCADV_C4_W16_ASM
-#define PCADV_C4_W16_ASM 1  // A/B builds: 0 = the in-loop screening builds its keys in C++
-#endif
 // values [V0, V0 + CNT) of pair PP's eight (tile 2 PP + (v >> 2), reg v & 3)
 // pushed into a span's top-2 with the asm keys and one v_med3_i32 per value
 // (hipcc spends seven instructions per value on the C++ form, this is five).
@@ -1262,16 +1161,12 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
       acc[cs][0] = mfma16_bf16(ah0, bh[kb], acc[cs][0]);
       acc[cs][1] = mfma16_bf16(ah1, bh[kb], acc[cs][1]);
       if constexpr (decltype(SCREEN)::value) {
-        if constexpr (PCADV_C4_W16_ASM) {
-          // 3 + 3 + 2 values over k-blocks 1..3; none in k-block 0, so the
-          // previous pair's MFMAs have retired before the asm reads them
-          // (tools/check_asm_hazards.py checks the distance in the ISA)
-          if (kb == 1) c4w_screen_asm<PREV::value, 0, 3>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
-          if (kb == 2) c4w_screen_asm<PREV::value, 3, 3>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
-          if (kb == 3) c4w_screen_asm<PREV::value, 6, 2>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
-        } else {
-          screen(PREV{}, 2 * kb, 2);
-        }
+        // 3 + 3 + 2 values over k-blocks 1..3; none in k-block 0, so the
+        // previous pair's MFMAs have retired before the asm reads them
+        // (tools/check_asm_hazards.py checks the distance in the ISA)
+        if (kb == 1) c4w_screen_asm<PREV::value, 0, 3>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
+        if (kb == 2) c4w_screen_asm<PREV::value, 3, 3>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
+        if (kb == 3) c4w_screen_asm<PREV::value, 6, 2>(acc[cs ^ 1], m_ord, m_hi, k1, k2);
         // pin the keys to this region (otherwise the IR passes sink the whole
         // screening below the MFMAs, next to its only use)
         asm volatile("" ::"v"(k1), "v"(k2));
@@ -1412,17 +1307,6 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
   }
 }
 
-#endif  // PCADV_C4_W16
-
-#if PCADV_C4_CERT
-// diagnostic builds only: read (and reset) the certification counters
-int c4_cert_read(unsigned* host) {
-  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_c4_cert), sizeof(g_c4_cert)) != hipSuccess) return -1;
-  const unsigned z[4] = {0, 0, 0, 0};
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_c4_cert), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 size_t feat_fwd_workspace_bytes(int C, int N) {
   (void)C;
   (void)N;
@@ -1433,16 +1317,23 @@ template <int NP3, int NP4>
 static int feat_fwd_attrs() {
   static bool attr_set = false;
   if (!attr_set) {
-#if PCADV_C4_W16
-    if constexpr (NP4 == 3) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, C4W16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)sizeof(C4Lds)) != hipSuccess) {
-        set_error("feat_fwd: cannot reserve LDS (%zu bytes)", sizeof(C4Lds));
-        return PCADV_EHIP;
-      }
+    // the N % 128 == 0 forms: fp32 mode's 16-channel waves, bf16 mode's P128
+    bool p128_ok;
+    if constexpr (NP4 == 3)
+      p128_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, C4W16>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)sizeof(C4Lds)) == hipSuccess;
+    else
+      p128_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, false, false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)sizeof(C4Lds)) == hipSuccess &&
+                hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, false, true, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)sizeof(C4Lds)) == hipSuccess;
+    if (!p128_ok) {
+      set_error("feat_fwd: cannot reserve LDS (%zu bytes)", sizeof(C4Lds));
+      return PCADV_EHIP;
     }
-#endif
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sizeof(C4Lds)) != hipSuccess ||
@@ -1453,12 +1344,6 @@ static int feat_fwd_attrs() {
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sizeof(C4Lds)) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, true, NP4 == 1>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(C4Lds)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, false, false, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(C4Lds)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv4_max<NP4, false, NP4 == 1, true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sizeof(C4Lds)) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(k_point_mlp<NP3, 2, false>),
@@ -1491,24 +1376,17 @@ static int launch_conv4_max_np(const float* x3, int C, int N, const float* w4, c
   if (rc != PCADV_OK) return rc;
   // two wave groups per 128-channel workgroup when 256-channel workgroups would
   // leave CUs idle (the diagnostic stamps layout assumes the plain form)
-#ifndef PCADV_C4_G2_MAXC
-#define PCADV_C4_G2_MAXC 63  // A/B builds: the largest cloud count run in the two-group form
-#endif
-  if (C <= PCADV_C4_G2_MAXC && !stamps)
+  if (C <= C4_G2_MAXC && !stamps)
     hipLaunchKernelGGL((k_conv4_max<NP4, true, XB>), dim3(C * (2 * C4_O / C4_CB)),
                        dim3(c4_threads<NP4, true, XB>()),
                        sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
-  else if (PCADV_C4_P128 && N % 128 == 0 && !stamps) {
-#if PCADV_C4_W16  // fp32 mode: 16-channel waves on 16x16x32 MFMAs, four waves per SIMD
-    if constexpr (NP4 == 3 && !XB) {
+  else if (N % 128 == 0 && !stamps) {
+    if constexpr (NP4 == 3)  // fp32 mode: 16-channel waves on 16x16x32 MFMAs, four waves per SIMD
       hipLaunchKernelGGL((k_conv4_max<NP4, C4W16>), dim3(C * (C4_O / C4_CB)), dim3(C4W_T),
                          sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
-      PC_HIP_CHECK_LAUNCH("k_conv4_max");
-      return PCADV_OK;
-    }
-#endif
-    hipLaunchKernelGGL((k_conv4_max<NP4, false, XB, true>), dim3(C * (C4_O / C4_CB)), dim3(C4_T),
-                       sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
+    else
+      hipLaunchKernelGGL((k_conv4_max<NP4, false, XB, true>), dim3(C * (C4_O / C4_CB)), dim3(C4_T),
+                         sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
   } else
     hipLaunchKernelGGL((k_conv4_max<NP4, false, XB>), dim3(C * (C4_O / C4_CB)), dim3(C4_T),
                        sizeof(C4Lds), s, x3, C, N, w4, b4, gmax, gidx, stamps, relu);
@@ -1529,10 +1407,7 @@ static int launch_feat_fwd_np(const float* pts_a, const float* pts_b, int split,
   uint64_t* mlp_stamps = stamps ? stamps + (size_t)C * (C4_O / C4_CB) * 16 : nullptr;
   // one tile per workgroup when two would give fewer than two workgroups per
   // CU (512); the diagnostic stamps layout assumes two
-#ifndef PCADV_MLP_ONE_BELOW
-#define PCADV_MLP_ONE_BELOW 1024  // A/B builds: the tile count below which one tile per workgroup runs
-#endif
-  const bool one = ntiles < PCADV_MLP_ONE_BELOW && !stamps;
+  const bool one = ntiles < PM_ONE_BELOW && !stamps;
   const dim3 grid(one ? ntiles : (ntiles + 1) / 2);
   auto kern = one ? (gf.n ? k_point_mlp<NP3, 1, true> : k_point_mlp<NP3, 1, false>)
                   : (gf.n ? k_point_mlp<NP3, 2, true> : k_point_mlp<NP3, 2, false>);

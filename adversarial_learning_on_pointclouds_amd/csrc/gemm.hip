@@ -76,7 +76,9 @@ struct GemmP {
   // row stride in elements), split once by its producer: staged as plain
   // copies (no VALU split per tile)
   const __bf16* ap[2]; long long ldap;
-  const __bf16* bp[3]; long long ldbp;  // TB = 3: hi, mid, lo (the three-way split)
+  // (bp[2] is unused; its slot keeps the later kernel arguments at their
+  // offsets, so the code of every kernel that takes a GemmP is unchanged)
+  const __bf16* bp[3]; long long ldbp;
   __bf16* cp[2]; long long ldcp;    // nullable: the epilogue also writes C's hi / lo planes
   // max-over-points screening epilogue (mode 2): per (row tile, column) top-2
   int2* part;                      // [M / BM][N] screening keys
@@ -335,12 +337,8 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
   // (planes: hi and lo resources, A's at this cloud's rows in mode 2)
   const __amdgpu_buffer_rsrc_t ars = rsrc(TA == 2 ? (const void*)(p.ap[0] + aoff2) : (const void*)Ab);
   const __amdgpu_buffer_rsrc_t arsl = rsrc(TA == 2 ? (const void*)(p.ap[1] + aoff2) : (const void*)Ab);
-  const __amdgpu_buffer_rsrc_t brs = rsrc(TB >= 2 ? (const void*)p.bp[0] : (const void*)p.b);
-  const __amdgpu_buffer_rsrc_t brsl = rsrc(TB >= 2 ? (const void*)p.bp[1] : (const void*)p.b);
-  // TB = 3: B as the hi / mid / lo planes of its three-way split (split once per
-  // step by pcadv_split_bf3, bitwise split_planes<3> of the f32 value), staged
-  // as plain copies; same LDS image, so the same MFMAs on the same values
-  const __amdgpu_buffer_rsrc_t brs3 = rsrc(TB == 3 ? (const void*)p.bp[2] : (const void*)p.b);
+  const __amdgpu_buffer_rsrc_t brs = rsrc(TB == 2 ? (const void*)p.bp[0] : (const void*)p.b);
+  const __amdgpu_buffer_rsrc_t brsl = rsrc(TB == 2 ? (const void*)p.bp[1] : (const void*)p.b);
   constexpr bool vecA = (VEC & 1) != 0, vecB = (VEC & 2) != 0;
   auto load_rows = [&](f32x4 (&v)[4], const __amdgpu_buffer_rsrc_t& rs, long long ld, int row0,
                        int rlim, int k0, auto VECT) {
@@ -430,26 +428,6 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
     v[2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rl, o, 0, 0));
     v[3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rl, o + 16u, 0, 0));
   };
-  // three planes: v[0..1] = hi, v[2..3] = mid, v[4..5] = lo
-  auto load_planes3 = [&](f32x4 (&v)[6], long long ld, int row0, int rlim, int k0) {
-    const int row = row0 + (tid >> 1), k = k0 + 16 * (tid & 1);
-    const bool ok = row < rlim && k >= kz0 && k < kz1;
-    const uint32_t o = opq(ok ? (uint32_t)((long long)row * ld + k) * 2u : OOB);
-    v[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brs, o, 0, 0));
-    v[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brs, o + 16u, 0, 0));
-    v[2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brsl, o, 0, 0));
-    v[3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brsl, o + 16u, 0, 0));
-    v[4] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brs3, o, 0, 0));
-    v[5] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brs3, o + 16u, 0, 0));
-  };
-  auto store_planes3 = [&](const f32x4 (&v)[6], __bf16 (*planes)[GM_BM * GM_S]) {
-    const int row = tid >> 1, kk = 16 * (tid & 1);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      *reinterpret_cast<f32x4*>(&planes[q][row * GM_S + kk]) = v[2 * q];
-      *reinterpret_cast<f32x4*>(&planes[q][row * GM_S + kk + 8]) = v[2 * q + 1];
-    }
-  };
   auto store_planes = [&](const f32x4 (&v)[4], __bf16 (*planes)[GM_BM * GM_S]) {
     const int row = tid >> 1, kk = 16 * (tid & 1);
 #pragma unroll
@@ -463,8 +441,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
     if (TA == 2) load_planes(ra, ars, arsl, p.ldap, m0, Mlim, k0);
     else if (TA == 0) load_rows(ra, ars, p.lda, m0, Mlim, k0, std::integral_constant<bool, vecA>{});
     else load_cols(ra, ars, p.lda, m0, Mlim, k0, std::integral_constant<bool, vecA>{});
-    if constexpr (TB == 3) load_planes3(rb, p.ldbp, n0, p.N, k0);
-    else if constexpr (TB == 2) load_planes(rb, brs, brsl, p.ldbp, n0, p.N, k0);
+    if constexpr (TB == 2) load_planes(rb, brs, brsl, p.ldbp, n0, p.N, k0);
     else if constexpr (TB == 0) load_rows(rb, brs, p.ldb, n0, p.N, k0, std::integral_constant<bool, vecB>{});
     else load_cols(rb, brs, p.ldb, n0, p.N, k0, std::integral_constant<bool, vecB>{});
   };
@@ -478,8 +455,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
         for (int i = 0; i < 4; ++i) cs[i] += ((ra[0][i] + ra[1][i]) + ra[2][i]) + ra[3][i];
       }
     }
-    if constexpr (TB == 3) store_planes3(rb, L.b);
-    else if constexpr (TB == 2) store_planes(rb, L.b);
+    if constexpr (TB == 2) store_planes(rb, L.b);
     else if constexpr (TB == 0) store_rows(rb, L.b);
     else store_cols(rb, L.b);
   };
@@ -600,7 +576,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
   // one register set: tile t + 1 is loaded right after tile t is stored; the
   // sched_barrier keeps those loads ahead of tile t's MFMAs (as
   // k_gemm_bf2_big), so one tile's MFMAs cover the next tile's loads
-  f32x4 ra[4], rb[TB == 3 ? 6 : 4];
+  f32x4 ra[4], rb[4];
   load_tile(ra, rb, kz0);
   for (int k0 = kz0; k0 < kz1; k0 += GM_BK) {
     __syncthreads();  // every wave is done reading the previous tile
@@ -726,16 +702,12 @@ k_gemm_x3_pair(GemmP pw, PairGeom gw, GemmP pd, PairGeom gd, int wfirst) {
 constexpr int GB_BM = 256, GB_BN = 256;
 constexpr int GB_T = 512;
 constexpr int GB_ES = 132;  // row stride (floats) of the staged 256 x 128 epilogue half
-#ifndef PCADV_GEMM_BIG_DB
-#define PCADV_GEMM_BIG_DB 1
-#endif
-constexpr int GB_NBUF = PCADV_GEMM_BIG_DB ? 2 : 1;  // LDS operand buffers (2: 160 KB, the whole LDS)
 struct GemmBigLds {
   union {
     struct {
       alignas(16) __bf16 a[2][GB_BM * GM_S];  // [hi, lo][m][k]
       alignas(16) __bf16 b[2][GB_BN * GM_S];  // [hi, lo][n][k]
-    } op[GB_NBUF];
+    } op[2];  // two operand buffers: 160 KB, the whole LDS
     alignas(16) float stage[GB_BM * GB_ES];
   };
 };
@@ -944,7 +916,6 @@ k_gemm_bf2_big(GemmP p) {
   // the scheduler otherwise sinks them below the MFMAs, where their registers
   // free up, and every store then waits out a full L2 round trip)
   f32x4 ra[4], rb[4];
-#if PCADV_GEMM_BIG_DB
   // two LDS buffers, one barrier per tile: tile t + 1 is stored into the
   // other buffer while tile t's MFMAs run (its loads were issued one tile
   // earlier), and tile t + 2's loads go out right after that store
@@ -962,17 +933,6 @@ k_gemm_bf2_big(GemmP p) {
     __syncthreads();
     buf ^= 1;
   }
-#else
-  load_tile(ra, rb, 0);
-  for (int k0 = 0; k0 < K; k0 += GM_BK) {
-    __syncthreads();
-    store_tile(ra, rb, 0);
-    __syncthreads();
-    load_tile(ra, rb, k0 + GM_BK);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_tile(0);
-  }
-#endif
   }
 
   if constexpr (MODE == 2) {
@@ -1580,23 +1540,12 @@ static int gemm_slot_flush(PendingGemm& slot, hipStream_t s) {
                      : gemm_launch_direct<0, 1, 1, 3, 3>(p, g, s);
 }
 
-// which GEMM's workgroups a pair dispatches first: the weight gradient's
-// (its slab workgroups run the longest; A/B on two boxes 1.139 -> 1.125 and
-// 1.182 -> 1.167 ms against the issue order); PCADV_PAIR_WFIRST=0: the data
-// gradient's, =i: the GEMM issued first.  Outputs bitwise the same either way.
-static int pair_wfirst(int issued) {
-  static const int v = [] {
-    const char* e = getenv("PCADV_PAIR_WFIRST");
-    if (e && e[0] == '0') return 0;
-    if (e && e[0] == 'i') return -1;
-    return 1;
-  }();
-  return v < 0 ? issued : v;
-}
+// A pair dispatches the weight gradient's workgroups first, whichever GEMM was
+// issued first: its slab workgroups run the longest (A/B on two boxes 1.139 ->
+// 1.125 and 1.182 -> 1.167 ms against the issue order).  Outputs are bitwise
+// the same either way.
 template <int VW, int MD, int VD, int NPD>
-static int gemm_pair_launch(const GemmP& pw, dim3 gw, const GemmP& pd, dim3 gd, int wfirst,
-                            hipStream_t s) {
-  wfirst = pair_wfirst(wfirst);
+static int gemm_pair_launch(const GemmP& pw, dim3 gw, const GemmP& pd, dim3 gd, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
     PC_TRY_GEMM(gemm_lds_attr(k_gemm_x3_pair<VW, MD, VD, NPD>));
@@ -1604,7 +1553,7 @@ static int gemm_pair_launch(const GemmP& pw, dim3 gw, const GemmP& pd, dim3 gd, 
   }
   const PairGeom a = pair_geom(gw), b = pair_geom(gd);
   hipLaunchKernelGGL((k_gemm_x3_pair<VW, MD, VD, NPD>), dim3((unsigned)(a.n + b.n)), dim3(GM_T),
-                     sizeof(GemmLds), s, pw, a, pd, b, wfirst);
+                     sizeof(GemmLds), s, pw, a, pd, b, /*wfirst=*/1);
   PC_HIP_CHECK_LAUNCH("k_gemm_x3_pair");
   return PCADV_OK;
 }
@@ -1622,23 +1571,23 @@ static int gemm_launch_v(const GemmP& p, dim3 grid, hipStream_t s, PendingGemm* 
           const dim3 gd = slot->grid;
           if (slot->np == 6) {
             if (slot->mode == 0)
-              return slot->v == 2 ? gemm_pair_launch<VEC, 0, 2, 6>(p, grid, pd, gd, 0, s)
-                                  : gemm_pair_launch<VEC, 0, 3, 6>(p, grid, pd, gd, 0, s);
-            return slot->v == 2 ? gemm_pair_launch<VEC, 1, 2, 6>(p, grid, pd, gd, 0, s)
-                                : gemm_pair_launch<VEC, 1, 3, 6>(p, grid, pd, gd, 0, s);
+              return slot->v == 2 ? gemm_pair_launch<VEC, 0, 2, 6>(p, grid, pd, gd, s)
+                                  : gemm_pair_launch<VEC, 0, 3, 6>(p, grid, pd, gd, s);
+            return slot->v == 2 ? gemm_pair_launch<VEC, 1, 2, 6>(p, grid, pd, gd, s)
+                                : gemm_pair_launch<VEC, 1, 3, 6>(p, grid, pd, gd, s);
           }
           if (slot->mode == 0)
-            return slot->v == 2 ? gemm_pair_launch<VEC, 0, 2, 3>(p, grid, pd, gd, 0, s)
-                                : gemm_pair_launch<VEC, 0, 3, 3>(p, grid, pd, gd, 0, s);
-          return slot->v == 2 ? gemm_pair_launch<VEC, 1, 2, 3>(p, grid, pd, gd, 0, s)
-                              : gemm_pair_launch<VEC, 1, 3, 3>(p, grid, pd, gd, 0, s);
+            return slot->v == 2 ? gemm_pair_launch<VEC, 0, 2, 3>(p, grid, pd, gd, s)
+                                : gemm_pair_launch<VEC, 0, 3, 3>(p, grid, pd, gd, s);
+          return slot->v == 2 ? gemm_pair_launch<VEC, 1, 2, 3>(p, grid, pd, gd, s)
+                              : gemm_pair_launch<VEC, 1, 3, 3>(p, grid, pd, gd, s);
         } else {
           const GemmP& pw = slot->p;
           const dim3 gw = slot->grid;
           switch (slot->v) {
-            case 1: return gemm_pair_launch<1, MODE, VEC, NP>(pw, gw, p, grid, 1, s);
-            case 2: return gemm_pair_launch<2, MODE, VEC, NP>(pw, gw, p, grid, 1, s);
-            default: return gemm_pair_launch<3, MODE, VEC, NP>(pw, gw, p, grid, 1, s);
+            case 1: return gemm_pair_launch<1, MODE, VEC, NP>(pw, gw, p, grid, s);
+            case 2: return gemm_pair_launch<2, MODE, VEC, NP>(pw, gw, p, grid, s);
+            default: return gemm_pair_launch<3, MODE, VEC, NP>(pw, gw, p, grid, s);
           }
         }
       }
@@ -1817,69 +1766,6 @@ int launch_split_bf2(const float* x, long long ld, int rows, int cols, void* hi,
   return PCADV_OK;
 }
 
-// f32 [rows][cols] -> bf16 hi / mid / lo planes (split_planes<3>: bitwise the
-// three-way split the six-product GEMMs make of an f32 operand per tile); hi and
-// mid are also the two-way split's hi / lo (split_planes<2>)
-__global__ void __launch_bounds__(256)
-k_split_bf3(const float* __restrict__ x, long long ld, int rows, int cols, __bf16* __restrict__ hi,
-            __bf16* __restrict__ mid, __bf16* __restrict__ lo, long long ldo) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (long long)rows * cols) return;
-  const int r = (int)(e / cols), c = (int)(e % cols);
-  __bf16 o[3];
-  split_planes<3>(x[(size_t)r * ld + c], o);
-  const size_t d = (size_t)r * ldo + c;
-  hi[d] = o[0];
-  mid[d] = o[1];
-  lo[d] = o[2];
-}
-
-int launch_split_bf3(const float* x, long long ld, int rows, int cols, void* hi, void* mid,
-                     void* lo, long long ldo, hipStream_t s) {
-  PC_REQUIRE(x && hi && mid && lo && rows > 0 && cols > 0 && ld >= cols && ldo >= cols,
-             "split_bf3: bad arguments");
-  const long long n = (long long)rows * cols;
-  hipLaunchKernelGGL(k_split_bf3, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ld, rows,
-                     cols, static_cast<__bf16*>(hi), static_cast<__bf16*>(mid),
-                     static_cast<__bf16*>(lo), ldo);
-  PC_HIP_CHECK_LAUNCH("k_split_bf3");
-  return PCADV_OK;
-}
-
-// The six-product GEMM C[M][N] (+)= A B^T with A f32 [m][k] (split three ways
-// per tile, as launch_gemm with precise = 1, ta = tb = 0) and B given as the
-// hi / mid / lo planes of its three-way split ([n][k], made once by
-// pcadv_split_bf3): the same MFMAs on the same values, so C is bitwise
-// launch_gemm's, without B's per-tile VALU split.
-int launch_gemm_b3(const float* a, long long lda, const void* b_hi, const void* b_mid,
-                   const void* b_lo, long long ldb, float* c, long long ldc, int M, int N, int K,
-                   const float* bias, const float* bias_rows, int rows_per_group, int relu,
-                   int accumulate, hipStream_t s) {
-  PC_REQUIRE(a && b_hi && b_mid && b_lo && c && M > 32 && N > 0 && K > 0,
-             "gemm_b3: bad shape M=%d N=%d K=%d (M > 32)", M, N, K);
-  PC_REQUIRE(K % 16 == 0 && ldb % 8 == 0 && ldb >= K && lda >= K,
-             "gemm_b3: K %% 16 and ldb %% 8 required (K=%d ldb=%lld)", K, ldb);
-  PC_REQUIRE((((uintptr_t)b_hi | (uintptr_t)b_mid | (uintptr_t)b_lo) & 15) == 0,
-             "gemm_b3: planes must be 16-B aligned");
-  PC_REQUIRE(((uintptr_t)a & 3) == 0 && ((uintptr_t)c & 3) == 0, "gemm_b3: float alignment");
-  PC_REQUIRE(ldc >= N && (!bias_rows || rows_per_group > 0), "gemm_b3: bad ldc / bias_rows");
-  PC_REQUIRE(fits31(M, lda, 4) && fits31(N, ldb, 2) && fits31(M, ldc, 4),
-             "gemm_b3: operands must span < 2 GB");
-  GemmP p{};
-  p.a = a; p.lda = lda;
-  p.bp[0] = static_cast<const __bf16*>(b_hi); p.bp[1] = static_cast<const __bf16*>(b_mid);
-  p.bp[2] = static_cast<const __bf16*>(b_lo); p.ldbp = ldb;
-  p.c = c; p.ldc = ldc;
-  p.bias = bias; p.bias_rows = bias_rows; p.rows_per_group = rows_per_group;
-  p.M = M; p.N = N; p.K = K; p.relu = relu; p.accumulate = accumulate;
-  p.avec = lda % 4 == 0 && ((uintptr_t)a & 15) == 0;
-  p.bvec = 1;
-  p.cvec = ldc % 4 == 0 && ((uintptr_t)c & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0) &&
-           (!bias_rows || (N % 4 == 0 && ((uintptr_t)bias_rows & 15) == 0));
-  p.grp = K; p.zpg = 1; p.ksplit_len = K;
-  return accumulate ? gemm_launch<0, 3, 1, 6>(p, 1, s) : gemm_launch<0, 3, 0, 6>(p, 1, s);
-}
-
 // weight gradient dW[O][Kin] (+)= sum over the rows of dZ[row][o] X[row][k]:
 // A = dZ^T (stored [rows][O], row stride ldz), B = X^T (stored [rows][Kin],
 // ldx); the row axis is cut into fixed-order slabs (zpg per group of
@@ -1887,33 +1773,16 @@ int launch_gemm_b3(const float* a, long long lda, const void* b_hi, const void* 
 // forms db[o] (+)= sum dZ[.][o] and the per-group sums gsum[g][o] from the
 // column sums the slabs take of the staged dZ.  Enough slabs to give the
 // launch ~768 workgroups, each slab at least 128 rows.
-#ifndef PCADV_WGRAD_WGS
-#define PCADV_WGRAD_WGS 512  // one dispatch round (two 61 KB-LDS workgroups per CU)
-#endif
-#ifndef PCADV_WGRAD_FLOOR
-#define PCADV_WGRAD_FLOOR 0
-#endif
 struct WgradPlan { int groups, grp, zpg, len, nz; };
-// the workgroups a weight gradient's slab plan aims at (PCADV_WGRAD_WGS
-// overrides the default, read once: the workspace size follows the plan)
-static int wgrad_wgs() {
-  static const int v = [] {
-    const char* e = getenv("PCADV_WGRAD_WGS");
-    const int x = e ? atoi(e) : 0;
-    return x > 0 ? x : PCADV_WGRAD_WGS;
-  }();
-  return v;
-}
+// the workgroups a weight gradient's slab plan aims at: one dispatch round
+// (two 61 KB-LDS workgroups per CU)
+constexpr int WGRAD_WGS = 512;
 static WgradPlan wgrad_plan(int rows, int O, int Kin, int rows_per_group) {
   WgradPlan w{};
   w.grp = rows_per_group > 0 ? rows_per_group : rows;
   w.groups = rows / w.grp;
   const int tiles = ((O + GM_BM - 1) / GM_BM) * ((Kin + GM_BN - 1) / GM_BN);
-#if PCADV_WGRAD_FLOOR
-  const int want = max(1, wgrad_wgs() / (tiles * w.groups));
-#else
-  const int want = (wgrad_wgs() + tiles * w.groups - 1) / (tiles * w.groups);
-#endif
+  const int want = (WGRAD_WGS + tiles * w.groups - 1) / (tiles * w.groups);
   w.zpg = max(1, min(want, (w.grp + 127) / 128));
   w.len = (w.grp + w.zpg - 1) / w.zpg;
   w.zpg = (w.grp + w.len - 1) / w.len;

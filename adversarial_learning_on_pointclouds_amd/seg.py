@@ -31,7 +31,6 @@ tests/test_gpu_seg.py holds the tolerances.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 import torch.nn as nn
@@ -46,16 +45,12 @@ __all__ = ["PointNetSeg", "SegTrainStep", "SegAdvTrainStep", "seg_cross_entropy"
 
 _LOC = 960                       # x1..x5 widths 64 + 128 + 128 + 128 + 512
 PRECISIONS = ("fp32", "bf16x3")
+# _PLANES, _PAIR and _DEFER are not options: they are the seams through which
+# tests/test_gpu_seg.py holds each form bitwise to the older one it replaced.
 # bf16x3 mode: the forward's operands as bf16 hi / lo planes written once by
-# their producers (pcadv_gemm_bf2; bitwise the f32-staged result);
-# PCADV_SEG_PLANES=0 stages f32
-_PLANES = os.environ.get("PCADV_SEG_PLANES", "1") == "1"
-# fp32 mode: the forward GEMMs' weights as hi / mid / lo planes split once per
-# step (pcadv_split_bf3 + pcadv_gemm_b3, bitwise the per-tile split).  Measured
-# slower (seg 1.183 -> 1.200 ms, profiles/r06_seg_b3_ab.txt: the plane copies
-# move 1.5x the f32 bytes per B tile, and the per-tile split they replace was
-# hidden under the MFMAs), so off unless PCADV_SEG_B3=1
-_B3 = os.environ.get("PCADV_SEG_B3", "0") == "1"
+# their producers (pcadv_gemm_bf2; bitwise the f32-staged result); False
+# stages f32
+_PLANES = True
 
 
 def _check_precision(precision):
@@ -108,21 +103,6 @@ class _Engine:
                                       None if bias_rows is None else _p(bias_rows),
                                       rows_per_group, int(relu), 0, None, 0, stream_ptr()),
               "pcadv_gemm_bf2")
-
-    def gemm_b3(self, a, lda, bp, ldb, c, ldc, M, N, K, *, bias=None, bias_rows=None,
-                rows_per_group=0, relu=False, a_off=0, c_off=0):
-        """The six-product (fp32-mode) GEMM with B as its (hi, mid, lo) planes."""
-        check(self.lib.pcadv_gemm_b3(_p(a, a_off), lda, _pb(bp[0]), _pb(bp[1]), _pb(bp[2]), ldb,
-                                     _p(c, c_off), ldc, M, N, K,
-                                     None if bias is None else _p(bias),
-                                     None if bias_rows is None else _p(bias_rows), rows_per_group,
-                                     int(relu), 0, stream_ptr()), "pcadv_gemm_b3")
-
-    def split3(self, x, hi, mid, lo):
-        """x f32 contiguous -> its hi, mid, lo bf16 planes (hi / mid = split's hi / lo)."""
-        r, c = (1, x.numel()) if x.dim() == 1 else (x.shape[0], x.shape[1])
-        check(self.lib.pcadv_split_bf3(_p(x), c, r, c, _pb(hi), _pb(mid), _pb(lo), c, stream_ptr()),
-              "pcadv_split_bf3")
 
     def split(self, x, hi, lo):
         """x (rows, cols) f32 contiguous -> hi, lo bf16 of the same shape."""
@@ -187,7 +167,7 @@ class _Engine:
 
     def wgrad_and_gemm(self, fin, wargs, wkw, g):
         """One layer's weight gradient (wgrad(*wargs, **wkw)) and its data gradient
-        g (a pcadv_gemm_desc): one paired launch, or two (PCADV_GEMM_PAIR=0)."""
+        g (a pcadv_gemm_desc): one paired launch, or two (_PAIR False)."""
         if _PAIR:
             self.wgrad(*wargs, fin=fin, pair=g, **wkw)
         else:
@@ -211,11 +191,10 @@ _ENGINE = None
 
 
 # weight gradients' finishing slab sums deferred and run in one launch at the
-# end of the backward (PCADV_WGRAD_DEFER=0: one launch after each, for A/B runs)
-_DEFER = os.environ.get("PCADV_WGRAD_DEFER", "1") != "0"
+# end of the backward (False: one launch after each)
+_DEFER = True
 # each layer's weight and data gradients in one launch (_Engine.pair)
-_PAIR = os.environ.get("PCADV_GEMM_PAIR", "1") != "0"
-_SMALL = os.environ.get("PCADV_WGRAD_SMALL", "1") != "0"  # fc1's per-cloud columns: exact f32 kernel
+_PAIR = True
 
 
 def _engine():
@@ -255,7 +234,7 @@ def _weight_planes(W, Wf, wplanes=None):
     return [None] + out[:5], out[5:]
 
 
-def seg_forward(pts, cls, params, wplanes=None, precision="fp32", wplanes3=None):
+def seg_forward(pts, cls, params, wplanes=None, precision="fp32"):
     """PointNetSeg forward (pointnet.py:282-317) on the engine.  Returns a dict
     with logits (B*N, C) point-major, gmax (B, 2048), gidx (B, 2048) and every
     activation the backward needs.  Each layer's epilogue also writes its
@@ -278,12 +257,6 @@ def seg_forward(pts, cls, params, wplanes=None, precision="fp32", wplanes3=None)
     # conv6's screen is three products in both modes (its winners are re-evaluated
     # in exact f32), staged from x5's planes: conv5's epilogue writes them
     c6p = _PLANES
-    # fp32 mode with the caller's three-way weight planes (list of 20 (hi, mid,
-    # lo) in state_dict order): the forward GEMMs stage B as plain copies
-    b3 = fp32 and wplanes3 is not None
-    if b3:
-        W3p = [None] + [tuple(t.view(W[i].shape) for t in wplanes3[2 * i]) for i in range(1, 5)]
-        Wf3p = [tuple(t.view(Wf[i].shape) for t in wplanes3[12 + 2 * i]) for i in range(4)]
     xloc = torch.empty(M, _LOC, device=dev)
     pl = lambda rows, cols: (torch.empty(rows, cols, device=dev, dtype=torch.bfloat16),  # noqa: E731
                              torch.empty(rows, cols, device=dev, dtype=torch.bfloat16))
@@ -302,9 +275,6 @@ def seg_forward(pts, cls, params, wplanes=None, precision="fp32", wplanes3=None)
         if planes:
             E.gemm_bf2(xp, _LOC, Wp[i], K, xloc, _LOC, M, O, K, bias=bc[i], relu=True,
                        a_off=_OFF[i - 1], c_off=_OFF[i], cp=xp, ldcp=_LOC, cp_off=_OFF[i])
-        elif b3 and not (i == 4 and c6p):
-            E.gemm_b3(xloc, _LOC, W3p[i], K, xloc, _LOC, M, O, K, bias=bc[i], relu=True,
-                      a_off=_OFF[i - 1], c_off=_OFF[i])
         else:
             last = i == 4 and c6p  # conv5 also writes x5's planes for conv6's screen
             E.gemm(xloc, _LOC, W[i], K, xloc, _LOC, M, O, K, bias=bc[i], relu=True,
@@ -345,12 +315,6 @@ def seg_forward(pts, cls, params, wplanes=None, precision="fp32", wplanes3=None)
         E.gemm_bf2(h2p, 256, Wfp[2], 256, h3, 128, M, 128, 256, bias=bf[2], relu=True, cp=h3p,
                    ldcp=128)
         E.gemm_bf2(h3p, 128, Wfp[3], 128, logits, ncls, M, ncls, 128, bias=bf[3])
-    elif b3:
-        E.gemm_b3(xloc, _LOC, Wf3p[0], 3024, h1, 256, M, 256, _LOC, bias_rows=cb,
-                  rows_per_group=N, relu=True)
-        E.gemm_b3(h1, 256, Wf3p[1], 256, h2, 256, M, 256, 256, bias=bf[1], relu=True)
-        E.gemm_b3(h2, 256, Wf3p[2], 256, h3, 128, M, 128, 256, bias=bf[2], relu=True)
-        E.gemm_b3(h3, 128, Wf3p[3], 128, logits, ncls, M, ncls, 128, bias=bf[3])
     else:
         E.gemm(xloc, _LOC, W1, 3024, h1, 256, M, 256, _LOC, bias_rows=cb, rows_per_group=N,
                relu=True, precise=pf)
@@ -414,14 +378,9 @@ def seg_backward(fw, dlogits, dgmax_out=None, out=None):
                      E.gemm_desc(dh1, 256, W1, 3024, dloc, _LOC, M, _LOC, 256, tb=1, cmask=xloc,
                                  ldm=_LOC, precise=pd))
     # the tiled global and class columns: B per-cloud rows, exact f32, one launch
-    if not _SMALL:
-        E.wgrad(s1, 256, gmax, 2048, B, 256, 2048, dW1, 3024, dw_off=960, fin=fin)
-        E.wgrad(s1, 256, cvec, cvec.shape[1], B, 256, cvec.shape[1], dW1, 3024, dw_off=3008,
-                fin=fin)
-    else:
-        check(E.lib.pcadv_wgrad_small(_p(s1), 256, B, 256, _p(gmax), 2048, 2048, _p(dW1, 960),
-                                      _p(cvec), cvec.shape[1], cvec.shape[1], _p(dW1, 3008), 3024,
-                                      0, stream_ptr()), "pcadv_wgrad_small")
+    check(E.lib.pcadv_wgrad_small(_p(s1), 256, B, 256, _p(gmax), 2048, 2048, _p(dW1, 960),
+                                  _p(cvec), cvec.shape[1], cvec.shape[1], _p(dW1, 3008), 3024,
+                                  0, stream_ptr()), "pcadv_wgrad_small")
     dg = torch.empty(B, 2048, device=dev)
     E.gemm(s1, 256, W1, 3024, dg, 2048, B, 2048, 256, tb=1, b_off=960, precise=pd)
     if dgmax_out is not None:
@@ -627,12 +586,6 @@ class SegTrainStep(_SegStep):
         super().__init__(model, (optimizer,), [(lr, betas, eps)], device, precision,
                          keep_activations)
         self.lambda_seg = float(lambda_seg)
-        # fp32 mode: the three-way split (hi, mid = wph, wpl, and lo), one launch
-        # per step, for the forward GEMMs' weight operands
-        self.wpl3 = torch.empty_like(self.wph) if _B3 else None
-        self.wplanes3 = ([(hi, mid, self.wpl3[o:o + hi.numel()])
-                          for (hi, mid), o in zip(self.wplanes, self.nets[0].offsets)]
-                         if _B3 else None)
         self.loss = torch.zeros((), device=self.device)
         self.graph = None
 
@@ -641,15 +594,12 @@ class SegTrainStep(_SegStep):
         _check_dev(pts, "pts")
         if seg.shape != (B, N) or seg.dtype != torch.int64 or not seg.is_contiguous():
             raise ValueError("seg: expected contiguous int64 (B, N)")
-        wpl = wpl3 = None
-        if _B3 and self.precision == "fp32":  # hi / mid / lo: conv6 reads hi / mid
-            _engine().split3(self.param, self.wph, self.wpl, self.wpl3)
-            wpl, wpl3 = (self.wplanes if _PLANES else None), self.wplanes3
-        elif _PLANES:  # every weight's planes (fp32 mode reads conv6's only)
+        wpl = None
+        if _PLANES:  # every weight's planes (fp32 mode reads conv6's only)
             _engine().split(self.param, self.wph, self.wpl)
             wpl = self.wplanes
         fw = seg_forward(pts, cls.float().reshape(B, 1, 16), self.params, wplanes=wpl,
-                         precision=self.precision, wplanes3=wpl3)
+                         precision=self.precision)
         if self.keep_activations:
             self.fw = fw  # the last step's activations (logits, x_global, argmax, ...)
         M, ncls = B * N, fw["dims"][2]

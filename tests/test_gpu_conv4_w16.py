@@ -1,7 +1,6 @@
 """k_conv4_max<3, C4W16>: fp32 mode's conv4 + max at 64 clouds or more and
 N % 128 == 0 (16 waves of 16 channels on 16x16x32 MFMAs, 128-point steps,
-top-2 keys per 64-point span, four lanes per channel; -DPCADV_C4_W16=0 builds
-run the P128 form there, which these tests hold to the same results).  The
+top-2 keys per 64-point span, four lanes per channel).  The
 smallest shapes that reach every path are C = 64 with N = 128 (one step: the
 prologue straight into the last screen), 256 (both LDS buffers) and 384 (a
 buffer reused).

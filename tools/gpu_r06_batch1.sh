@@ -1,7 +1,6 @@
 #!/bin/bash
 # One lease: the round-6 tests (fused feature-transform step, strict g13, DP),
-# the dp1 / adv_ft bench lines, the adv_ft and cls profiles, and the argmax
-# certification A/B.  A failing pytest (rc 1) does not stop the evidence steps;
+# the dp1 / adv_ft bench lines, and the adv_ft and cls profiles.  A failing pytest (rc 1) does not stop the evidence steps;
 # a time limit, abort or crash does.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
@@ -21,5 +20,4 @@ for s in dp1 adv_ft adv_ft_body; do
   if [ $r -ne 0 ]; then tail -30 gpurun_out/r06a_$s.log; exit $r; fi
 done
 bash tools/gpu_r06b.sh r06 || exit $?
-bash tools/gpu_cert_ab.sh r06_cert || exit $?
 exit $rc
