@@ -140,6 +140,25 @@ class PwdiscArgs(ctypes.Structure):
     ]
 
 
+class StackdiscArgs(ctypes.Structure):
+    """Mirror of pcadv_stackdisc_args (include/pcadv.h)."""
+
+    _fields_ = [
+        ("logits", _vp), ("ld", _i64),
+        ("ncls", _i), ("n0", _i), ("n1", _i), ("t0", _i), ("t1", _i),
+        ("w", _vp * 5), ("b", _vp * 5),
+        ("num_shapes", _i), ("shape_label", _vp), ("pts_per_cloud", _i),
+        ("lambda_disc_shape", _f),
+        ("m", _vp), ("argc", _vp), ("d_out", _vp), ("shape_logits", _vp), ("losses", _vp),
+        ("soft0", _vp), ("soft1", _vp), ("soft_out", _vp),
+        ("rng_seed", _u64), ("step_count", _vp),
+        ("dm_d", _vp), ("dm_adv", _vp), ("bad_rows", _vp), ("lambda_adv", _f),
+        ("dw", _vp * 5), ("db", _vp * 5),
+        ("dlogits", _vp), ("ldd", _i64), ("max_workgroups", _i),
+        ("workspace", _vp), ("workspace_bytes", _sz), ("x_out", _vp),
+    ]
+
+
 PWD_NONE, PWD_SOFTMAX, PWD_LOG_SOFTMAX = 0, 1, 2
 
 # name -> (restype, argtypes); every symbol of include/pcadv.h
@@ -217,6 +236,9 @@ SIGNATURES = {
     "pcadv_row_semi_ce_workspace_bytes": (_sz, [_i]),
     "pcadv_row_semi_ce": (_i, [_vp, _i64, _vp, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz,
                                _vp]),
+    "pcadv_stackdisc_workspace_bytes": (_sz, [_i64, _i]),
+    "pcadv_stackdisc_forward": (_i, [ctypes.POINTER(StackdiscArgs), _vp]),
+    "pcadv_stackdisc_backward": (_i, [ctypes.POINTER(StackdiscArgs), _vp]),
 }
 
 _lib = None

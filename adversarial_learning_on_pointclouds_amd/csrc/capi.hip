@@ -115,6 +115,9 @@ int launch_gather_multi(const pcadv_gather_job*, int, hipStream_t);
 size_t pwdisc_workspace_bytes(long long, int);
 int launch_pwdisc_fwd(const pcadv_pwdisc_args*, hipStream_t);
 int launch_pwdisc_bwd(const pcadv_pwdisc_args*, hipStream_t);
+size_t stackdisc_workspace_bytes(long long, int);
+int launch_stackdisc_fwd(const pcadv_stackdisc_args*, hipStream_t);
+int launch_stackdisc_bwd(const pcadv_stackdisc_args*, hipStream_t);
 size_t row_ce_workspace_bytes(int);
 int launch_row_ce(const float*, long long, const int64_t*, int, int, float, float*, float*, void*,
                   size_t, hipStream_t);
@@ -863,6 +866,18 @@ int pcadv_pwdisc_forward(const pcadv_pwdisc_args* args, hipStream_t stream) {
 
 int pcadv_pwdisc_backward(const pcadv_pwdisc_args* args, hipStream_t stream) {
   return launch_pwdisc_bwd(args, stream);
+}
+
+size_t pcadv_stackdisc_workspace_bytes(int64_t rows, int max_workgroups) {
+  return stackdisc_workspace_bytes(rows, max_workgroups);
+}
+
+int pcadv_stackdisc_forward(const pcadv_stackdisc_args* args, hipStream_t stream) {
+  return launch_stackdisc_fwd(args, stream);
+}
+
+int pcadv_stackdisc_backward(const pcadv_stackdisc_args* args, hipStream_t stream) {
+  return launch_stackdisc_bwd(args, stream);
 }
 
 }  // extern "C"

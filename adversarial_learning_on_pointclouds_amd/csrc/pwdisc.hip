@@ -10,6 +10,12 @@
 // the forward, so its recomputed activations (and ReLU masks) are the forward's
 // bits.  No floating-point atomics: the loss terms and the weight-gradient
 // slabs are summed in a fixed order.
+//
+// StackDiscNet (models/discriminator.py:139-175, run_training_seg_stack) shares
+// all of it: the layer functions and the backward are templates on the
+// activation (ReLU here, LeakyReLU(0.2) there), and k_stk_fwd adds conv5, the
+// logsumexp, out / (out + 1), the BCE and shape terms and conv5's gradients
+// behind the channel max (second half of this file).
 #include <cmath>
 
 #include "common.h"
@@ -142,8 +148,9 @@ __device__ __forceinline__ void pwd_frags_t(const float* __restrict__ w, int ldw
     for (int j = 0; j < 4; ++j) bf[g][j] = ok ? col[(size_t)(8 * g + 4 * h + j) * ldw] : 0.f;
 }
 
-// one 64 -> 64 layer + ReLU of the tile: wave = (row tile wave >> 1, column
-// tile wave & 1)
+// one 64 -> 64 layer + activation (ReLU, or the stacked discriminator's
+// LeakyReLU(0.2)) of the tile: wave = (row tile wave >> 1, column tile wave & 1)
+template <int ACT>
 __device__ __forceinline__ void pwd_layer64(const float* in, float* out, const f32x4 (&bf)[8],
                                             float bias, int wave, int lane) {
   const int r = lane & 31, oc = 32 * (wave & 1), rt = wave >> 1;
@@ -151,23 +158,24 @@ __device__ __forceinline__ void pwd_layer64(const float* in, float* out, const f
   acc = mfma_rows_x_wt<64>(in + 32 * rt * PD_S, PD_S, bf, acc, lane);
 #pragma unroll
   for (int e = 0; e < 16; ++e)
-    out[(32 * rt + acc_row(e, lane)) * PD_S + oc + r] = act_fwd(acc[e] + bias, ACT_RELU);
+    out[(32 * rt + acc_row(e, lane)) * PD_S + oc + r] = act_fwd(acc[e] + bias, ACT);
 }
 
 // x0 -> x1 -> x2 -> x3 (each [64][PD_S]); the caller has synchronised after
 // writing x0.  Ends with a barrier: x3 is readable by every wave.
+template <int ACT>
 __device__ __forceinline__ void pwd_chain3(const PwdNet& p, float* x0, float* x1, float* x2,
                                            float* x3, int wave, int lane) {
   const int r = lane & 31, oc = 32 * (wave & 1);
   f32x4 bf[8];
   pwd_frags<true>(p.w[0], p.ncls, p.ncls, oc, lane, bf);
-  pwd_layer64(x0, x1, bf, p.b[0][oc + r], wave, lane);
+  pwd_layer64<ACT>(x0, x1, bf, p.b[0][oc + r], wave, lane);
   pwd_frags<false>(p.w[1], 64, 64, oc, lane, bf);
   __syncthreads();
-  pwd_layer64(x1, x2, bf, p.b[1][oc + r], wave, lane);
+  pwd_layer64<ACT>(x1, x2, bf, p.b[1][oc + r], wave, lane);
   pwd_frags<false>(p.w[2], 64, 64, oc, lane, bf);
   __syncthreads();
-  pwd_layer64(x2, x3, bf, p.b[2][oc + r], wave, lane);
+  pwd_layer64<ACT>(x2, x3, bf, p.b[2][oc + r], wave, lane);
   __syncthreads();
 }
 
@@ -175,6 +183,50 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+
+// conv4 + activation of the tile x3 into y4 [64][PD_S4] (wave = 32 of the 128
+// channels, both row tiles), a barrier, then the max over the channels, first
+// index on ties: 4 lanes x 32 channels per row (row = tid >> 2).  All four
+// lanes of a row end with the same (best, bi).
+template <int ACT>
+__device__ __forceinline__ void pwd_conv4_max(const PwdNet& p, const float* x3, float* y4, int tid,
+                                              float& best, int& bi) {
+  const int lane = tid & 63, wave = tid >> 6, r = lane & 31;
+  {
+    f32x4 bf[8];
+    pwd_frags<false>(p.w[3], 64, 64, 32 * wave, lane, bf);
+    const float bias = p.b[3][32 * wave + r];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f32x16 acc = {};
+      acc = mfma_rows_x_wt<64>(x3 + 32 * t * PD_S, PD_S, bf, acc, lane);
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        y4[(32 * t + acc_row(e, lane)) * PD_S4 + 32 * wave + r] = act_fwd(acc[e] + bias, ACT);
+    }
+  }
+  __syncthreads();
+  const int row = tid >> 2, q = tid & 3;
+  const float* y = &y4[row * PD_S4 + 32 * q];
+  best = y[0];
+  bi = 32 * q;
+#pragma unroll 8
+  for (int c = 1; c < 32; ++c) {
+    const float v = y[c];
+    if (beats(v, best)) { best = v; bi = 32 * q + c; }
+  }
+#pragma unroll
+  for (int m = 1; m < 4; m <<= 1) {
+    const float ov = __shfl_xor(best, m);
+    const int oi = __shfl_xor(bi, m);
+    const bool up = q & m;  // this lane holds the higher channels
+    const float lo_v = up ? ov : best, hi_v = up ? best : ov;
+    const int lo_i = up ? oi : bi, hi_i = up ? bi : oi;
+    const bool t = beats(hi_v, lo_v);
+    best = t ? hi_v : lo_v;
+    bi = t ? hi_i : lo_i;
+  }
 }
 
 struct PwdFwdLds {
@@ -188,7 +240,7 @@ struct PwdFwdLds {
 __global__ void __launch_bounds__(PD_T, 2) k_pwd_fwd(PwdNet p, PwdFwdOut o, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   PwdFwdLds& L = *reinterpret_cast<PwdFwdLds*>(smem);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long M = (long long)p.n0 + p.n1;
   uint32_t stepv = 0;
   if (o.losses && o.step) stepv = (uint32_t)*o.step;
@@ -197,43 +249,12 @@ __global__ void __launch_bounds__(PD_T, 2) k_pwd_fwd(PwdNet p, PwdFwdOut o, int 
     pwd_load_x0(p, r0, tid, L.xa);
     __syncthreads();
     // xa -> xb -> xa -> xb
-    pwd_chain3(p, L.xa, L.xb, L.xa, L.xb, wave, lane);
-    {  // conv4 + ReLU: wave = 32 of the 128 channels, both row tiles
-      f32x4 bf[8];
-      pwd_frags<false>(p.w[3], 64, 64, 32 * wave, lane, bf);
-      const float bias = p.b[3][32 * wave + r];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        f32x16 acc = {};
-        acc = mfma_rows_x_wt<64>(L.xb + 32 * t * PD_S, PD_S, bf, acc, lane);
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-          L.y4[(32 * t + acc_row(e, lane)) * PD_S4 + 32 * wave + r] =
-              act_fwd(acc[e] + bias, ACT_RELU);
-      }
-    }
-    __syncthreads();
-    {  // max over the channels, first index on ties: 4 lanes x 32 channels
+    pwd_chain3<ACT_RELU>(p, L.xa, L.xb, L.xa, L.xb, wave, lane);
+    {
       const int row = tid >> 2, q = tid & 3;
-      const float* y = &L.y4[row * PD_S4 + 32 * q];
-      float best = y[0];
-      int bi = 32 * q;
-#pragma unroll 8
-      for (int c = 1; c < 32; ++c) {
-        const float v = y[c];
-        if (beats(v, best)) { best = v; bi = 32 * q + c; }
-      }
-#pragma unroll
-      for (int m = 1; m < 4; m <<= 1) {
-        const float ov = __shfl_xor(best, m);
-        const int oi = __shfl_xor(bi, m);
-        const bool up = q & m;  // this lane holds the higher channels
-        const float lo_v = up ? ov : best, hi_v = up ? best : ov;
-        const int lo_i = up ? oi : bi, hi_i = up ? bi : oi;
-        const bool t = beats(hi_v, lo_v);
-        best = t ? hi_v : lo_v;
-        bi = t ? hi_i : lo_i;
-      }
+      float best;
+      int bi;
+      pwd_conv4_max<ACT_RELU>(p, L.xb, L.y4, tid, best, bi);
       const long long g = (long long)r0 + row;
       if (q == 0) {
         float l0 = 0.f, l1 = 0.f, l2 = 0.f;
@@ -340,7 +361,9 @@ __device__ __forceinline__ f32x16 pwd_wgrad(const float* dz, const float* sv, co
   return acc;
 }
 
-// the data gradient of one layer: out = (in W) masked by relu'(y) (y = NULL: none)
+// the data gradient of one layer: out = (in W) masked by the activation's
+// derivative at y (relu: 1 / 0, leaky relu: 1 / 0.2; y = NULL: none)
+template <int ACT>
 __device__ __forceinline__ void pwd_dgrad(const float* in, float* out, const float* y,
                                           const f32x4 (&bf)[8], int wave, int lane) {
   const int r = lane & 31, oc = 32 * (wave & 1), rt = wave >> 1;
@@ -349,13 +372,19 @@ __device__ __forceinline__ void pwd_dgrad(const float* in, float* out, const flo
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int i = (32 * rt + acc_row(e, lane)) * PD_S + oc + r;
-    out[i] = (!y || y[i] > 0.f) ? acc[e] : 0.f;
+    if constexpr (ACT == ACT_RELU)
+      out[i] = (!y || y[i] > 0.f) ? acc[e] : 0.f;
+    else
+      out[i] = (!y || y[i] > 0.f) ? acc[e] : 0.2f * acc[e];
   }
 }
 
 // The whole backward of a row is linear in one scalar, so one unit chain per
 // row (gradient 1 at channel argc) serves both uses: the weight gradients scale
 // it by D's dout (sv), the no-GT rows' input gradient by lambda_adv dout_adv.
+// ACT_LRELU (the stacked discriminator): no row is dead, every mask is 1 / 0.2,
+// and the arg-max channel's own mask on out scales the row's two scalars.
+template <int ACT>
 __global__ void __launch_bounds__(PD_T, 1) k_pwd_bwd(PwdNet p, PwdBwdArgs a, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   PwdBwdLds& L = *reinterpret_cast<PwdBwdLds*>(smem);
@@ -371,13 +400,17 @@ __global__ void __launch_bounds__(PD_T, 1) k_pwd_bwd(PwdNet p, PwdBwdArgs a, int
     pwd_load_x0(p, r0, tid, L.x[0]);
     if (tid < PD_ROWS) {
       const long long g = (long long)r0 + tid;
-      const bool live = g < M && a.out[g] > 0.f;  // relu'(0) = 0: a dead row gets nothing
-      L.sv[tid] = live ? a.dout_d[g] : 0.f;
-      L.av[tid] = (live && want_dx && g >= p.n0) ? a.lambda_adv * a.dout_adv[g - p.n0] : 0.f;
+      const bool pos = g < M && a.out[g] > 0.f;
+      // relu'(0) = 0: a dead row gets nothing; a leaky row gets 0.2 of it
+      const bool live = ACT == ACT_RELU ? pos : g < M;
+      const float top = (ACT == ACT_RELU || pos) ? 1.f : 0.2f;
+      L.sv[tid] = live ? top * a.dout_d[g] : 0.f;
+      L.av[tid] =
+          (live && want_dx && g >= p.n0) ? top * (a.lambda_adv * a.dout_adv[g - p.n0]) : 0.f;
       L.ac[tid] = live ? (a.argc[g] & 127) : -1;  // a channel of conv4 whatever the buffer holds
     }
     __syncthreads();
-    pwd_chain3(p, L.x[0], L.x[1], L.x[2], L.x[3], wave, lane);
+    pwd_chain3<ACT>(p, L.x[0], L.x[1], L.x[2], L.x[3], wave, lane);
     if (a.x_out) {  // uniform over the grid
 #pragma unroll 4
       for (int j = 0; j < PD_ROWS * 64 / PD_T; ++j) {
@@ -408,7 +441,12 @@ __global__ void __launch_bounds__(PD_T, 1) k_pwd_bwd(PwdNet p, PwdBwdArgs a, int
     for (int j = 0; j < PD_ROWS * 64 / PD_T; ++j) {
       const int e = tid + PD_T * j, row = e >> 6, k = e & 63;
       const int c = L.ac[row];
-      L.da[row * PD_S + k] = (c >= 0 && L.x[3][row * PD_S + k] > 0.f) ? p.w[3][c * 64 + k] : 0.f;
+      if constexpr (ACT == ACT_RELU) {
+        L.da[row * PD_S + k] = (c >= 0 && L.x[3][row * PD_S + k] > 0.f) ? p.w[3][c * 64 + k] : 0.f;
+      } else {
+        const float w = c >= 0 ? p.w[3][c * 64 + k] : 0.f;
+        L.da[row * PD_S + k] = L.x[3][row * PD_S + k] > 0.f ? w : 0.2f * w;
+      }
     }
     f32x4 bf[8];
     pwd_frags_t(p.w[2], 64, 64, wk, lane, bf);
@@ -417,14 +455,14 @@ __global__ void __launch_bounds__(PD_T, 1) k_pwd_bwd(PwdNet p, PwdBwdArgs a, int
     g3 = pwd_wgrad(L.da, L.sv, L.x[2], wo, wk, g3, lane);
     if (wave == 0)
       for (int row = 0; row < PD_ROWS; ++row) bsum += L.sv[row] * L.da[row * PD_S + lane];
-    pwd_dgrad(L.da, L.db, L.x[2], bf, wave, lane);
+    pwd_dgrad<ACT>(L.da, L.db, L.x[2], bf, wave, lane);
     pwd_frags_t(p.w[1], 64, 64, wk, lane, bf);
     __syncthreads();
     // conv2
     g2 = pwd_wgrad(L.db, L.sv, L.x[1], wo, wk, g2, lane);
     if (wave == 1)
       for (int row = 0; row < PD_ROWS; ++row) bsum += L.sv[row] * L.db[row * PD_S + lane];
-    pwd_dgrad(L.db, L.da, L.x[1], bf, wave, lane);
+    pwd_dgrad<ACT>(L.db, L.da, L.x[1], bf, wave, lane);
     __syncthreads();
     // conv1
     g1 = pwd_wgrad(L.da, L.sv, L.x[0], wo, wk, g1, lane);
@@ -433,7 +471,7 @@ __global__ void __launch_bounds__(PD_T, 1) k_pwd_bwd(PwdNet p, PwdBwdArgs a, int
     const bool dx_tile = want_dx && (long long)r0 + PD_ROWS > p.n0;  // uniform over the workgroup
     if (dx_tile) {
       pwd_frags_t(p.w[0], p.ncls, p.ncls, wk, lane, bf);
-      pwd_dgrad(L.da, L.db, nullptr, bf, wave, lane);
+      pwd_dgrad<ACT>(L.da, L.db, nullptr, bf, wave, lane);
     }
     __syncthreads();
     if (dx_tile) {  // through the input transform, written to the no-GT rows only
@@ -513,6 +551,278 @@ __global__ void __launch_bounds__(256) k_pwd_bwd_finish(const float* __restrict_
     g.db[2][e - SL_B3] = s;
   } else {
     g.db[3][e - SL_B4] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// StackDiscNet (models/discriminator.py:139-175): the same four layers with
+// LeakyReLU(0.2), then per point S[s] = w5[s] m + b5[s], out = logsumexp_s S,
+// d_out = out / (out + 1), and run_training_seg_stack's BCE and shape terms
+// (utils/trainer.py:1097-1150).  Everything after m is a function of that one
+// scalar, so the backward is k_pwd_bwd<ACT_LRELU> on dm_d / dm_adv.
+// ---------------------------------------------------------------------------
+constexpr int SK_MAXS = 32;            // shape classes (the reference: 16)
+constexpr int SK_NTERM = 8;            // adv, D's GT part, its no-GT part, CE, bad rows
+constexpr int SK_NP = SK_NTERM + 2 * SK_MAXS;  // one workgroup's partial sums
+// per-row columns of the tile's scratch (the free x buffer): dL/dS, m, the terms
+constexpr int SK_CM = SK_MAXS, SK_CT = SK_MAXS + 1;
+
+struct StkFwdOut {
+  const float* w5;
+  const float* b5;
+  int S;
+  const int32_t* shape_label;
+  int ppc;
+  float lambda_shape;
+  float* m;
+  int32_t* argc;
+  float* d_out;
+  float* shape_logits;  // optional [M][S]
+  float* losses;        // [5] or NULL: no loss terms
+  const float* soft0;
+  const float* soft1;
+  float* soft_out;
+  uint64_t seed;
+  const int32_t* step;
+  float* dm_d;
+  float* dm_adv;
+  float* dw5;
+  float* db5;
+  int32_t* bad_rows;
+  unsigned* ticket;
+  float* partial;  // [SK_NP][gridDim.x]
+};
+
+// torch's binary_cross_entropy: the logs clamped at -100, the derivative's
+// denominator at 1e-12.  x outside [0, 1] (a log of a negative number) gives a
+// clamped NaN, never a fault; the row is counted in bad_rows.
+__device__ __forceinline__ float stk_bce(float lx, float l1x, float y) {
+  return -(y * lx + (1.f - y) * l1x);
+}
+
+__global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int ntiles) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  PwdFwdLds& L = *reinterpret_cast<PwdFwdLds*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long M = (long long)p.n0 + p.n1;
+  const int S = o.S;
+  uint32_t stepv = 0;
+  if (o.losses && o.step) stepv = (uint32_t)*o.step;
+  // wave 0's sums over this workgroup's tiles, in tile order: lane c < 32 holds
+  // db5[c], lane 32 + c dw5[c]; every lane the five terms
+  float gsum = 0.f, tsum[4] = {0.f, 0.f, 0.f, 0.f};
+  int nbad = 0;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int r0 = tile * PD_ROWS;
+    pwd_load_x0(p, r0, tid, L.xa);
+    __syncthreads();
+    pwd_chain3<ACT_LRELU>(p, L.xa, L.xb, L.xa, L.xb, wave, lane);  // xa is free from here
+    {
+      const int row = tid >> 2, q = tid & 3;
+      float best;
+      int bi;
+      pwd_conv4_max<ACT_LRELU>(p, L.xb, L.y4, tid, best, bi);
+      const long long g = (long long)r0 + row;
+      const bool in = g < M;
+      // conv5 and the logsumexp less the row maximum: lane q holds s = q + 4 j
+      float sv[SK_MAXS / 4], wv[SK_MAXS / 4], e[SK_MAXS / 4];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < SK_MAXS / 4; ++j) {
+        const int s = q + 4 * j;
+        const bool ok = s < S;
+        wv[j] = ok ? o.w5[s] : 0.f;
+        sv[j] = ok ? wv[j] * best + o.b5[s] : -INFINITY;
+        mx = fmaxf(mx, sv[j]);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 1));
+      mx = fmaxf(mx, __shfl_xor(mx, 2));
+      float sum = 0.f;
+#pragma unroll
+      for (int j = 0; j < SK_MAXS / 4; ++j) {
+        e[j] = q + 4 * j < S ? expf(sv[j] - mx) : 0.f;
+        sum += e[j];
+      }
+      sum += __shfl_xor(sum, 1);
+      sum += __shfl_xor(sum, 2);
+      const float out = mx + logf(sum);
+      const float x = out / (out + 1.f);
+      if (in) {
+        if (q == 0) {
+          o.m[g] = best;
+          o.argc[g] = bi;
+          o.d_out[g] = x;
+        }
+        if (o.shape_logits) {
+#pragma unroll
+          for (int j = 0; j < SK_MAXS / 4; ++j)
+            if (q + 4 * j < S) o.shape_logits[(size_t)g * S + q + 4 * j] = sv[j];
+        }
+      }
+      if (o.losses) {  // uniform over the grid
+        float t_adv = 0.f, t_gt = 0.f, t_ng = 0.f, t_ce = 0.f, t_bad = 0.f;
+        float ds[SK_MAXS / 4];
+#pragma unroll
+        for (int j = 0; j < SK_MAXS / 4; ++j) ds[j] = 0.f;
+        if (in) {
+          const float inv = 1.f / sum;
+          const float lx = fmaxf(logf(x), -100.f), l1x = fmaxf(log1pf(-x), -100.f);
+          const float den = fmaxf(x * (1.f - x), 1e-12f);
+          const float dxdo = 1.f / ((out + 1.f) * (out + 1.f));
+          t_bad = (x >= 0.f && x <= 1.f) ? 0.f : 1.f;
+          float gd, lam = 0.f;
+          int lab = -1;
+          if (g < p.n0) {
+            // make_D_label(random=True), one label per point (utils/utils.py:22-31)
+            const float y0 = o.soft0 ? o.soft0[g]
+                                     : 0.7f + 0.35f * rng_uniform(o.seed, stepv, RNG_LABEL_GT,
+                                                                  (uint32_t)g);
+            t_gt = stk_bce(lx, l1x, y0);
+            gd = 0.5f * ((x - y0) / den) * dxdo / (float)p.n0;
+            lab = o.shape_label[g / o.ppc];
+            lam = o.lambda_shape / (float)p.n0;
+            if (o.soft_out && q == 0) o.soft_out[g] = y0;
+          } else {
+            const long long jr = g - p.n0;
+            const float y1 = o.soft1 ? o.soft1[jr]
+                                     : 0.305f * rng_uniform(o.seed, stepv, RNG_LABEL_NOGT,
+                                                            (uint32_t)jr);
+            t_ng = stk_bce(lx, l1x, y1);
+            t_adv = stk_bce(lx, l1x, 1.f);  // against label 1 (the generator's term)
+            gd = 0.5f * ((x - y1) / den) * dxdo / (float)p.n1;
+            if (o.soft_out && q == 0) o.soft_out[g] = y1;
+          }
+          float pw = 0.f, dmd = 0.f, slab = 0.f;
+#pragma unroll
+          for (int j = 0; j < SK_MAXS / 4; ++j) {
+            const int s = q + 4 * j;
+            const float pj = e[j] * inv;
+            const bool hit = s == lab;
+            if (s < S) ds[j] = gd * pj + lam * (pj - (hit ? 1.f : 0.f));
+            if (hit && s < S) slab = sv[j];
+            pw += pj * wv[j];
+            dmd += ds[j] * wv[j];
+          }
+          pw += __shfl_xor(pw, 1);
+          pw += __shfl_xor(pw, 2);
+          dmd += __shfl_xor(dmd, 1);
+          dmd += __shfl_xor(dmd, 2);
+          slab += __shfl_xor(slab, 1);
+          slab += __shfl_xor(slab, 2);
+          if (g < p.n0) t_ce = out - slab;  // CrossEntropyLoss(S, shape label) of the row
+          if (q == 0) {
+            o.dm_d[g] = dmd;
+            if (g >= p.n0 && o.dm_adv)
+              o.dm_adv[g - p.n0] = ((x - 1.f) / den) * dxdo * pw / (float)p.n1;
+          }
+        }
+        float* sc = L.xa + row * PD_S;
+#pragma unroll
+        for (int j = 0; j < SK_MAXS / 4; ++j) sc[q + 4 * j] = ds[j];
+        if (q == 0) {
+          sc[SK_CM] = in ? best : 0.f;
+          sc[SK_CT + 0] = t_adv;
+          sc[SK_CT + 1] = t_gt;
+          sc[SK_CT + 2] = t_ng;
+          sc[SK_CT + 3] = t_ce;
+          sc[SK_CT + 4] = t_bad;
+        }
+      }
+    }
+    if (o.losses) {
+      __syncthreads();  // the scratch rows are written, y4 is read for the last time
+      {  // each wave sums a quarter of the rows in row order, wave 0 the quarters
+        const int c = lane & (SK_MAXS - 1);
+        const bool wgt = lane >= SK_MAXS;
+        float a = 0.f;
+#pragma unroll 4
+        for (int row = 16 * wave; row < 16 * wave + 16; ++row) {
+          const float v = L.xa[row * PD_S + c];
+          a += wgt ? v * L.xa[row * PD_S + SK_CM] : v;
+        }
+        L.y4[tid] = a;
+      }
+      float t5[5];
+      if (wave == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) t5[k] = wave_sum(L.xa[lane * PD_S + SK_CT + k]);
+      }
+      __syncthreads();  // the next tile's x0 goes to xa
+      if (wave == 0) {
+        gsum += ((L.y4[lane] + L.y4[64 + lane]) + L.y4[128 + lane]) + L.y4[192 + lane];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tsum[k] += t5[k];
+        nbad += (int)t5[4];
+      }
+      // y4 is written again after three more barriers
+    }
+  }
+  if (!o.losses) return;
+  const int G = gridDim.x;
+  if (wave == 0) {
+    o.partial[(size_t)(SK_NTERM + lane) * G + blockIdx.x] = gsum;
+    if (lane < 4) o.partial[(size_t)lane * G + blockIdx.x] = tsum[lane];
+    if (lane == 4) o.partial[(size_t)4 * G + blockIdx.x] = __int_as_float(nbad);
+  }
+  // the last workgroup to arrive sums the workgroups' terms in workgroup order
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    const unsigned t = atomicAdd(o.ticket, 1u);
+    L.last = t == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!L.last) return;  // uniform over the workgroup
+  __threadfence();
+  // Sum k of the 4 + 2 S (the four terms, db5, dw5) belongs to wave k & 3: each
+  // lane adds every 64th workgroup's value, all of a wave's sums in one pass so
+  // that their loads are in flight together, then a butterfly.
+  const unsigned* part = reinterpret_cast<const unsigned*>(o.partial);
+  constexpr int KU = (4 + 2 * SK_MAXS) / 4;
+  const int nsum = 4 + 2 * S;
+  float acc[KU];
+#pragma unroll
+  for (int u = 0; u < KU; ++u) acc[u] = 0.f;
+  for (int t = lane; t < G; t += 64) {
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+      const int k = wave + 4 * u;
+      // partial's row: terms 0..3, db5[j] at SK_NTERM + j, dw5[j] at SK_NTERM + 32 + j
+      const int row = k < 4 ? k : k - 4 < S ? SK_NTERM + k - 4 : SK_NTERM + SK_MAXS + (k - 4 - S);
+      if (k < nsum)
+        acc[u] += __uint_as_float(__hip_atomic_load(part + (size_t)row * G + t, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT));
+    }
+  }
+  float* fin = &L.lt[0][0];  // 4 + 2 S <= 68 sums
+#pragma unroll
+  for (int u = 0; u < KU; ++u) {
+    const int k = wave + 4 * u;
+    const float v = wave_sum(acc[u]);
+    if (k < nsum && lane == 0) fin[k] = v;
+  }
+  int bad = 0;
+  if (wave == 0) {
+    for (int t = lane; t < G; t += 64)
+      bad += (int)__hip_atomic_load(part + (size_t)4 * G + t, __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) bad += __shfl_xor(bad, o2);
+  }
+  __syncthreads();
+  if (tid < 2 * S) (tid < S ? o.db5 : o.dw5)[tid < S ? tid : tid - S] = fin[4 + tid];
+  if (tid == 0) {
+    const float* term = fin;
+    const float adv = p.n1 ? term[0] / (float)p.n1 : 0.f;
+    const float dgt = p.n0 ? 0.5f * (term[1] / (float)p.n0) : 0.f;
+    const float dng = p.n1 ? 0.5f * (term[2] / (float)p.n1) : 0.f;
+    o.losses[0] = adv;        // loss_adv
+    o.losses[1] = dgt + dng;  // loss_D
+    o.losses[2] = dgt;
+    o.losses[3] = dng;
+    o.losses[4] = p.n0 ? term[3] / (float)p.n0 : 0.f;  // loss_D_shape, unscaled
+    *o.bad_rows = bad;
+    *o.ticket = 0u;  // ready for the next launch
   }
 }
 
@@ -638,11 +948,162 @@ int launch_pwdisc_bwd(const pcadv_pwdisc_args* a, hipStream_t s) {
   b.x_out = a->x_out;
   b.slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + WS_HEAD +
                                      pwd_partial_bytes(nt));
-  static int once = pwd_lds(k_pwd_bwd, sizeof(PwdBwdLds), "k_pwd_bwd");  // see launch_pwdisc_fwd
+  static int once = pwd_lds(k_pwd_bwd<ACT_RELU>, sizeof(PwdBwdLds), "k_pwd_bwd");  // see launch_pwdisc_fwd
   if (once) return once;
   const int grid = pwd_grid(nt, a->max_workgroups, PD_BWD_WG);
-  hipLaunchKernelGGL(k_pwd_bwd, dim3(grid), dim3(PD_T), sizeof(PwdBwdLds), s, p, b, nt);
+  hipLaunchKernelGGL(k_pwd_bwd<ACT_RELU>, dim3(grid), dim3(PD_T), sizeof(PwdBwdLds), s, p, b, nt);
   PC_HIP_CHECK_LAUNCH("k_pwd_bwd");
+  hipLaunchKernelGGL(k_pwd_bwd_finish, dim3((SL_N + 255) / 256), dim3(256), 0, s, b.slabs, grid,
+                     a->ncls, g);
+  PC_HIP_CHECK_LAUNCH("k_pwd_bwd_finish");
+  return PCADV_OK;
+}
+
+}  // namespace pcadv
+
+// ---------------------------------------------------------------------------
+// StackDiscNet: host side
+// ---------------------------------------------------------------------------
+namespace pcadv {
+
+namespace {
+
+size_t stk_partial_bytes(int grid) { return ((size_t)grid * SK_NP * 4 + 255) / 256 * 256; }
+
+int stk_check(const pcadv_stackdisc_args* a, const char* what, PwdNet& p) {
+  PC_REQUIRE(a, "%s: args is NULL", what);
+  PC_REQUIRE(a->ncls >= 2 && a->ncls <= 64, "%s: ncls = %d, expected 2..64", what, a->ncls);
+  PC_REQUIRE(a->num_shapes >= 2 && a->num_shapes <= SK_MAXS, "%s: num_shapes = %d, expected 2..%d",
+             what, a->num_shapes, SK_MAXS);
+  PC_REQUIRE(a->n0 >= 0 && a->n1 >= 0 && (long long)a->n0 + a->n1 >= 1 &&
+                 (long long)a->n0 + a->n1 <= 0x7fffffffLL - PD_ROWS,
+             "%s: row counts n0 = %d, n1 = %d", what, a->n0, a->n1);
+  PC_REQUIRE(a->ld >= a->ncls, "%s: row stride ld = %lld < ncls = %d", what, (long long)a->ld,
+             a->ncls);
+  PC_REQUIRE(a->t0 >= 0 && a->t0 <= 2 && a->t1 >= 0 && a->t1 <= 2,
+             "%s: transforms (%d, %d): PCADV_PWD_NONE / _SOFTMAX / _LOG_SOFTMAX", what, a->t0,
+             a->t1);
+  PC_REQUIRE(a->max_workgroups >= 0, "%s: max_workgroups = %d", what, a->max_workgroups);
+  PC_REQUIRE(a->logits && a->m && a->argc, "%s: logits, m and argc are required", what);
+  for (int i = 0; i < 5; ++i) {
+    PC_REQUIRE(a->w[i] && a->b[i], "%s: conv%d's weight and bias are required", what, i + 1);
+    PC_REQUIRE(i == 0 || i == 4 || ((uintptr_t)a->w[i] & 15) == 0,
+               "%s: conv%d's weight is not 16-B aligned", what, i + 1);
+    if (i < 4) {
+      p.w[i] = a->w[i];
+      p.b[i] = a->b[i];
+    }
+  }
+  p.logits = a->logits;
+  p.ld = a->ld;
+  p.ncls = a->ncls;
+  p.n0 = a->n0;
+  p.n1 = a->n1;
+  p.t0 = a->t0;
+  p.t1 = a->t1;
+  return PCADV_OK;
+}
+
+}  // namespace
+
+size_t stackdisc_workspace_bytes(long long rows, int max_wg) {
+  if (rows < 1) return 0;
+  const int nt = pwd_tiles(rows);
+  return WS_HEAD + stk_partial_bytes(pwd_grid(nt, max_wg, PD_FWD_WG)) +
+         (size_t)pwd_grid(nt, max_wg, PD_BWD_WG) * SL_N * 4;
+}
+
+int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, hipStream_t s) {
+  const char* what = "pcadv_stackdisc_forward";
+  PwdNet p;
+  if (int rc = stk_check(a, what, p)) return rc;
+  const long long rows = (long long)a->n0 + a->n1;
+  const int nt = pwd_tiles(rows);
+  const int grid = pwd_grid(nt, a->max_workgroups, PD_FWD_WG);
+  PC_REQUIRE(a->d_out, "%s: d_out is required", what);
+  StkFwdOut o = {};
+  o.w5 = a->w[4];
+  o.b5 = a->b[4];
+  o.S = a->num_shapes;
+  o.m = a->m;
+  o.argc = a->argc;
+  o.d_out = a->d_out;
+  o.shape_logits = a->shape_logits;
+  o.ppc = 1;
+  if (a->losses) {
+    PC_REQUIRE(a->dm_d && a->dw[4] && a->db[4] && a->bad_rows,
+               "%s: losses need dm_d, conv5's dw / db and bad_rows", what);
+    if (a->n0 > 0) {
+      PC_REQUIRE(a->shape_label && a->pts_per_cloud >= 1 && a->n0 % a->pts_per_cloud == 0,
+                 "%s: the GT rows need shape_label and a pts_per_cloud (%d) that divides n0 = %d",
+                 what, a->pts_per_cloud, a->n0);
+      o.ppc = a->pts_per_cloud;
+    }
+    const bool drawn = (a->n0 > 0 && !a->soft0) || (a->n1 > 0 && !a->soft1);
+    PC_REQUIRE(!drawn || a->step_count, "%s: device-drawn labels need step_count", what);
+    PC_REQUIRE(a->workspace &&
+                   a->workspace_bytes >= stackdisc_workspace_bytes(rows, a->max_workgroups),
+               "%s: workspace of %zu bytes, need %zu", what, a->workspace_bytes,
+               stackdisc_workspace_bytes(rows, a->max_workgroups));
+    o.shape_label = a->shape_label;
+    o.lambda_shape = a->lambda_disc_shape;
+    o.losses = a->losses;
+    o.soft0 = a->soft0;
+    o.soft1 = a->soft1;
+    o.soft_out = a->soft_out;
+    o.seed = a->rng_seed;
+    o.step = a->step_count;
+    o.dm_d = a->dm_d;
+    o.dm_adv = a->dm_adv;
+    o.dw5 = a->dw[4];
+    o.db5 = a->db[4];
+    o.bad_rows = a->bad_rows;
+    o.ticket = reinterpret_cast<unsigned*>(a->workspace);
+    o.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + WS_HEAD);
+  }
+  static int once = pwd_lds(k_stk_fwd, sizeof(PwdFwdLds), "k_stk_fwd");  // see launch_pwdisc_fwd
+  if (once) return once;
+  hipLaunchKernelGGL(k_stk_fwd, dim3(grid), dim3(PD_T), sizeof(PwdFwdLds), s, p, o, nt);
+  PC_HIP_CHECK_LAUNCH("k_stk_fwd");
+  return PCADV_OK;
+}
+
+int launch_stackdisc_bwd(const pcadv_stackdisc_args* a, hipStream_t s) {
+  const char* what = "pcadv_stackdisc_backward";
+  PwdNet p;
+  if (int rc = stk_check(a, what, p)) return rc;
+  const long long rows = (long long)a->n0 + a->n1;
+  const int nt = pwd_tiles(rows);
+  PC_REQUIRE(a->dm_d, "%s: dm_d is required", what);
+  PwdGrads g;
+  for (int i = 0; i < 4; ++i) {
+    PC_REQUIRE(a->dw[i] && a->db[i], "%s: conv%d's gradients are required", what, i + 1);
+    g.dw[i] = a->dw[i];
+    g.db[i] = a->db[i];
+  }
+  PC_REQUIRE(!a->dlogits || a->ldd >= a->ncls, "%s: dlogits stride %lld < ncls", what,
+             (long long)a->ldd);
+  PC_REQUIRE(a->workspace &&
+                 a->workspace_bytes >= stackdisc_workspace_bytes(rows, a->max_workgroups),
+             "%s: workspace of %zu bytes, need %zu", what, a->workspace_bytes,
+             stackdisc_workspace_bytes(rows, a->max_workgroups));
+  PwdBwdArgs b;
+  b.out = a->m;
+  b.argc = a->argc;
+  b.dout_d = a->dm_d;
+  b.dout_adv = a->dm_adv;
+  b.lambda_adv = a->lambda_adv;
+  b.dlogits = a->dlogits;
+  b.ldd = a->ldd;
+  b.x_out = a->x_out;
+  b.slabs = reinterpret_cast<float*>(
+      reinterpret_cast<char*>(a->workspace) + WS_HEAD +
+      stk_partial_bytes(pwd_grid(nt, a->max_workgroups, PD_FWD_WG)));
+  static int once = pwd_lds(k_pwd_bwd<ACT_LRELU>, sizeof(PwdBwdLds), "k_pwd_bwd<lrelu>");
+  if (once) return once;
+  const int grid = pwd_grid(nt, a->max_workgroups, PD_BWD_WG);
+  hipLaunchKernelGGL(k_pwd_bwd<ACT_LRELU>, dim3(grid), dim3(PD_T), sizeof(PwdBwdLds), s, p, b, nt);
+  PC_HIP_CHECK_LAUNCH("k_pwd_bwd<lrelu>");
   hipLaunchKernelGGL(k_pwd_bwd_finish, dim3((SL_N + 255) / 256), dim3(256), 0, s, b.slabs, grid,
                      a->ncls, g);
   PC_HIP_CHECK_LAUNCH("k_pwd_bwd_finish");

@@ -7,7 +7,14 @@ layers on B x C x 1 with LeakyReLU(0.2), then Linear(64, output_dim).
 PointwiseDiscNet (:53-79), the per-point discriminator of run_training_seg
 (utils/trainer.py:849-1026): conv1..conv4 + ReLU and the max over the 128
 channels, one logit per point, fused in csrc/pwdisc.hip (pwdisc_forward /
-pwdisc_backward below are the thin calls into it)."""
+pwdisc_backward below are the thin calls into it).
+
+StackDiscNet (:139-175), the stacked shape discriminator of
+run_training_seg_stack (utils/trainer.py:1028-1216): the same four layers with
+LeakyReLU(0.2), the max over the 128 channels, conv5 = Conv1d(1, num_shapes, 1)
+on that one value per point (the shape logits) and disc_out = lse / (lse + 1)
+with lse their logsumexp; stackdisc_forward / stackdisc_backward call the fused
+kernels (csrc/pwdisc.hip, the k_stk_fwd part)."""
 from __future__ import annotations
 
 import ctypes
@@ -21,9 +28,11 @@ from ._lib import ptr as _vp
 from .ops import ACT_LRELU, ACT_NONE, LinearFunction
 
 __all__ = ["DeepConvDiscNet", "PointwiseDiscNet", "pwdisc_forward", "pwdisc_backward",
-           "pwdisc_workspace", "PWD_NONE", "PWD_SOFTMAX", "PWD_LOG_SOFTMAX"]
+           "pwdisc_workspace", "PWD_NONE", "PWD_SOFTMAX", "PWD_LOG_SOFTMAX", "StackDiscNet",
+           "stackdisc_forward", "stackdisc_backward", "stackdisc_workspace"]
 
 PWD_MAX_DIM = 64  # input channels the fused kernels take (the MFMA's padded K)
+STACK_MAX_SHAPES = 32  # shape classes the fused stacked discriminator takes
 
 
 class DeepConvDiscNet(nn.Module):
@@ -218,3 +227,190 @@ class PointwiseDiscNet(nn.Module):
             raise ValueError(f"x: pcadv ops run on the HIP device only (got {x.device})")
         out, _ = _PointwiseDisc.apply(x, *[p for _, p in self.named_parameters()])
         return out.view(-1, self.input_pts)
+
+
+def stackdisc_workspace(rows, device, max_workgroups=0, zero=True):
+    """The workspace the stacked discriminator's forward and backward of `rows`
+    points share (zeroed once for the forward's ticket, as pwdisc_workspace)."""
+    n = max(int(_lib.load().pcadv_stackdisc_workspace_bytes(int(rows), int(max_workgroups))), 256)
+    return (torch.zeros if zero else torch.empty)(n, device=device, dtype=torch.uint8)
+
+
+def _i32(t, name, numel):
+    if t.dtype != torch.int32 or t.numel() != numel or t.device.type != "cuda" \
+            or not t.is_contiguous():
+        raise TypeError(f"{name}: expected {numel} contiguous int32 on the HIP device")
+    return t
+
+
+def _stack_args(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, max_workgroups):
+    rows = n0 + n1
+    if logits.dim() != 2 or logits.shape[0] != rows or logits.shape[1] < ncls \
+            or logits.stride(1) != 1:
+        raise ValueError(f"logits: expected point-major ({rows}, >= {ncls}) rows, "
+                         f"got {tuple(logits.shape)} with strides {logits.stride()}")
+    if logits.device.type != "cuda" or logits.dtype != torch.float32:
+        raise TypeError("logits: expected torch.float32 on the HIP device")
+    if not 2 <= ncls <= PWD_MAX_DIM:
+        raise ValueError(f"ncls: the fused discriminator takes 2..{PWD_MAX_DIM} channels, got {ncls}")
+    if len(params) != 10:
+        raise ValueError("params: expected conv1..conv5's weights and biases (10 tensors)")
+    S = params[9].numel()
+    if not 2 <= S <= STACK_MAX_SHAPES:
+        raise ValueError(f"num_shapes: the fused discriminator takes 2..{STACK_MAX_SHAPES}, got {S}")
+    shapes = [64 * ncls, 64, 4096, 64, 4096, 64, 8192, 128, S, S]
+    a = _lib.StackdiscArgs()
+    for i, (p, n) in enumerate(zip(params, shapes)):
+        _f32(p, f"D parameter {i}", n)
+        if i % 2 == 0:
+            a.w[i // 2] = p.data_ptr()
+        else:
+            a.b[i // 2] = p.data_ptr()
+    a.logits, a.ld = _vp(logits), logits.stride(0) if rows > 1 else max(logits.stride(0), ncls)
+    a.ncls, a.n0, a.n1, a.t0, a.t1, a.num_shapes = ncls, n0, n1, int(t0), int(t1), S
+    a.m, a.argc = _vp(_f32(m, "m", rows)), _vp(_i32(argc, "argc", rows))
+    a.max_workgroups = int(max_workgroups)
+    if ws is not None:
+        a.workspace, a.workspace_bytes = _vp(ws), ws.numel()
+    return a, S
+
+
+def stackdisc_forward(logits, ncls, n0, n1, t0, t1, params, m, argc, d_out, ws, *,
+                      shape_logits=None, losses=None, shape_label=None, pts_per_cloud=0,
+                      lambda_disc_shape=1.0, soft0=None, soft1=None, soft_out=None, seed=0,
+                      step_count=None, dm_d=None, dm_adv=None, grads5=None, bad_rows=None,
+                      max_workgroups=0):
+    """pcadv_stackdisc_forward on the current stream (include/pcadv.h): m, argc,
+    d_out, optionally shape_logits (rows, num_shapes), and, with `losses` (5
+    floats), the BCE and shape terms with dm_d / dm_adv, conv5's gradients
+    grads5 = (dw5, db5) and the int32 bad_rows counter."""
+    a, S = _stack_args(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, max_workgroups)
+    a.d_out = _vp(_f32(d_out, "d_out", n0 + n1))
+    if shape_logits is not None:
+        a.shape_logits = _vp(_f32(shape_logits, "shape_logits", (n0 + n1) * S))
+    if losses is not None:
+        a.losses = _vp(_f32(losses, "losses", 5))
+        if n0:
+            if pts_per_cloud < 1 or n0 % pts_per_cloud:
+                raise ValueError(f"pts_per_cloud = {pts_per_cloud} does not divide the {n0} GT rows")
+            a.shape_label = _vp(_i32(shape_label, "shape_label", n0 // pts_per_cloud))
+            a.pts_per_cloud = int(pts_per_cloud)
+        a.lambda_disc_shape = float(lambda_disc_shape)
+        a.soft0 = _vp(None if soft0 is None else _f32(soft0, "soft0", n0))
+        a.soft1 = _vp(None if soft1 is None else _f32(soft1, "soft1", n1))
+        a.soft_out = _vp(None if soft_out is None else _f32(soft_out, "soft_out", n0 + n1))
+        a.rng_seed = int(seed)
+        a.step_count = _vp(step_count)
+        a.dm_d = _vp(_f32(dm_d, "dm_d", n0 + n1))
+        a.dm_adv = _vp(None if dm_adv is None else _f32(dm_adv, "dm_adv", n1))
+        a.dw[4] = _f32(grads5[0], "conv5's weight gradient", S).data_ptr()
+        a.db[4] = _f32(grads5[1], "conv5's bias gradient", S).data_ptr()
+        a.bad_rows = _vp(_i32(bad_rows, "bad_rows", 1))
+    check(_lib.load().pcadv_stackdisc_forward(ctypes.byref(a), stream_ptr()),
+          "pcadv_stackdisc_forward")
+
+
+def stackdisc_backward(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, dm_d, grads, *,
+                       dm_adv=None, lambda_adv=1.0, dlogits=None, max_workgroups=0, x_out=None):
+    """pcadv_stackdisc_backward on the current stream: the first eight of
+    `grads` (conv1..conv4, state_dict order) are written, and rows
+    [n0, n0 + n1) of `dlogits` when it and dm_adv are given.  x_out
+    (3, n0 + n1, 64), optional, receives the recomputed x1..x3."""
+    a, _ = _stack_args(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, max_workgroups)
+    a.dm_d = _vp(_f32(dm_d, "dm_d", n0 + n1))
+    a.dm_adv = _vp(None if dm_adv is None else _f32(dm_adv, "dm_adv", n1))
+    a.lambda_adv = float(lambda_adv)
+    for i, (g, p) in enumerate(zip(grads[:8], params[:8])):
+        _f32(g, f"D gradient {i}", p.numel())
+        if i % 2 == 0:
+            a.dw[i // 2] = g.data_ptr()
+        else:
+            a.db[i // 2] = g.data_ptr()
+    if x_out is not None:
+        a.x_out = _vp(_f32(x_out, "x_out", 3 * (n0 + n1) * 64))
+    if dlogits is not None:
+        if dlogits.dim() != 2 or dlogits.shape[0] != n0 + n1 or dlogits.shape[1] < ncls \
+                or dlogits.stride(1) != 1 or dlogits.dtype != torch.float32 \
+                or dlogits.device.type != "cuda":
+            raise ValueError("dlogits: expected point-major float32 rows like logits")
+        a.dlogits, a.ldd = _vp(dlogits), max(dlogits.stride(0), ncls)
+    check(_lib.load().pcadv_stackdisc_backward(ctypes.byref(a), stream_ptr()),
+          "pcadv_stackdisc_backward")
+
+
+class _StackDiscMax(torch.autograd.Function):
+    """x (B, C, N) -> m (B * N,), the channel max of lrelu(conv4(..)): the fused
+    forward, and the fused backward scaled per row by the incoming gradient.
+    conv5 and the logsumexp after it are 16 numbers per point and stay in torch,
+    so both of the module's outputs are differentiable through this one node.
+    The kernel also forms d_out per row; on this path it is discarded, and the
+    module's disc_out is torch's value computed from m, not the kernel's."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        B, C, N = x.shape
+        rows = _point_major(x.detach())
+        M = B * N
+        m = torch.empty(M, device=x.device)
+        d = torch.empty(M, device=x.device)
+        argc = torch.empty(M, device=x.device, dtype=torch.int32)
+        ps = [p.detach().contiguous() for p in params]
+        stackdisc_forward(rows, C, 0, M, PWD_NONE, PWD_NONE, ps, m, argc, d, None)
+        ctx.save_for_backward(rows, m, argc, *ps)
+        ctx.dims = (B, C, N)
+        return m
+
+    @staticmethod
+    def backward(ctx, dm):
+        rows, m, argc, *ps = ctx.saved_tensors
+        B, C, N = ctx.dims
+        M = B * N
+        d = dm.reshape(M).contiguous().float()
+        grads = [torch.empty_like(p) for p in ps[:8]]
+        need_dx = ctx.needs_input_grad[0]
+        dl = torch.empty(M, C, device=rows.device) if need_dx else None
+        ws = stackdisc_workspace(M, rows.device, zero=False)
+        stackdisc_backward(rows, C, 0, M, PWD_NONE, PWD_NONE, ps, m, argc, ws, d, grads,
+                           dm_adv=d if need_dx else None, lambda_adv=1.0, dlogits=dl)
+        dx = dl.view(B, N, C).permute(0, 2, 1) if need_dx else None
+        return (dx, *grads, None, None)  # conv5 acts after this node
+
+
+class StackDiscNet(nn.Module):
+    """models/discriminator.py:139-175.  forward(x: B x input_dim x N) ->
+    (shape_logits B x num_shapes x N, disc_out B x N x 1)."""
+
+    def __init__(self, input_pts, input_dim, num_shapes):
+        super().__init__()
+        if not 2 <= int(input_dim) <= PWD_MAX_DIM:
+            raise ValueError(f"input_dim: the fused discriminator takes 2..{PWD_MAX_DIM} "
+                             f"channels, got {input_dim}")
+        if not 2 <= int(num_shapes) <= STACK_MAX_SHAPES:
+            raise ValueError(f"num_shapes: the fused discriminator takes 2..{STACK_MAX_SHAPES} "
+                             f"shape classes, got {num_shapes}")
+        if int(input_pts) < 1:
+            raise ValueError(f"input_pts: expected a positive point count, got {input_pts}")
+        self.input_pts = int(input_pts)
+        self.input_dim = int(input_dim)
+        self.num_shapes = int(num_shapes)
+        self.conv1 = nn.Conv1d(input_dim, 64, 1)
+        self.conv2 = nn.Conv1d(64, 64, 1)
+        self.conv3 = nn.Conv1d(64, 64, 1)
+        self.conv4 = nn.Conv1d(64, 128, 1)
+        self.conv5 = nn.Conv1d(1, num_shapes, 1)
+
+    def check_input(self, x):
+        if x.dim() != 3 or x.shape[1] != self.input_dim:
+            raise ValueError(f"x: expected B x {self.input_dim} x N, got {tuple(x.shape)}")
+        if not x.is_floating_point() or x.dtype != torch.float32:
+            raise TypeError(f"x: expected torch.float32, got {x.dtype}")
+
+    def forward(self, x):
+        self.check_input(x)
+        if x.device.type != "cuda":
+            raise ValueError(f"x: pcadv ops run on the HIP device only (got {x.device})")
+        B, _, N = x.shape
+        m = _StackDiscMax.apply(x, *[p for _, p in self.named_parameters()])
+        shape_logits = self.conv5(m.view(B, 1, N))  # B x S x N
+        out = torch.logsumexp(shape_logits.transpose(2, 1), dim=2, keepdim=True)
+        return shape_logits, out / (out + 1.0)

@@ -6,7 +6,7 @@ import sys
 import torch
 from torch.nn import init
 
-from .discriminator import DeepConvDiscNet, PointwiseDiscNet
+from .discriminator import DeepConvDiscNet, PointwiseDiscNet, StackDiscNet
 from .pointnet import PointNetCls
 
 
@@ -55,8 +55,9 @@ def init_weights(net, init_type, init_gain=1.0, verbose=True):
 
 def load_models(mode, device, args):
     """utils/model_utils.py:60-140 for the hot path's modes 'cls' and 'disc', the
-    segmentation row's 'seg' and its per-point discriminator 'disc_seg'.
-    The dual / stacked discriminators are outside this build's scope."""
+    segmentation row's 'seg', its per-point discriminator 'disc_seg' and the
+    stacked shape discriminator 'disc_stack'.  The dual discriminator and the
+    regularised generator are outside this build's scope."""
     if mode == "cls":
         model = PointNetCls(k=40, feature_transform=False).to(device)
         try:
@@ -83,7 +84,10 @@ def load_models(mode, device, args):
     elif mode == "disc_seg":  # :113-115, PointwiseDiscNet (run_training_seg's D)
         model = PointwiseDiscNet(input_pts=args.input_pts, input_dim=args.disc_indim)
         model = init_net(model, device, init_type=args.init_disc)
-    elif mode in ("seg_regu", "disc_dual", "disc_stack"):
+    elif mode == "disc_stack":  # StackDiscNet (run_training_seg_stack's D)
+        model = StackDiscNet(input_pts=args.input_pts, input_dim=args.disc_indim, num_shapes=16)
+        model = init_net(model, device, init_type=args.init_disc)
+    elif mode in ("seg_regu", "disc_dual"):
         raise NotImplementedError(f"mode {mode!r} is outside the adversarial cls hot path")
     else:
         raise ValueError("Invalid mode {}!".format(mode))

@@ -40,8 +40,8 @@ from ._lib import check, stream_ptr
 from .flat import FlatAdam
 from .step import FusedStep
 
-__all__ = ["PointNetSeg", "SegTrainStep", "SegAdvTrainStep", "seg_cross_entropy", "seg_forward",
-           "seg_backward"]
+__all__ = ["PointNetSeg", "SegTrainStep", "SegAdvTrainStep", "SegStackTrainStep",
+           "seg_cross_entropy", "seg_forward", "seg_backward"]
 
 _LOC = 960                       # x1..x5 widths 64 + 128 + 128 + 128 + 512
 PRECISIONS = ("fp32", "bf16x3")
@@ -778,4 +778,139 @@ class SegAdvTrainStep(_SegStep):
         the warm-up).  `semi` is baked into the graph."""
         def body():
             self(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True, semi)
+        return self._capture(body, body)
+
+
+class SegStackTrainStep(_SegStep):
+    """One iteration of run_training_seg_stack (utils/trainer.py:1053-1153) with
+    ImagePool(0), PointNetSeg + StackDiscNet and two Adams, as native launches
+    on one stream, capturable into a HIP graph:
+
+      weight-plane split; seg_forward on the 2B clouds [GT; no-GT];
+      pcadv_row_ce on the GT rows (scale lambda_seg); the shape labels
+      (argmax of cls_gt, one per GT cloud) on the device; the fused stacked D
+      forward on softmax(GT) / log_softmax(no-GT) (trainer.py:1082,1095) with
+      loss_adv, loss_D, loss_D_shape, their derivatives with respect to the
+      per-point channel max, conv5's gradients and the bad_rows counter; the
+      fused D backward (conv1..conv4's gradients of loss_D + lambda_disc_shape
+      loss_D_shape, and the no-GT rows of dlogits from lambda_adv loss_adv
+      through the frozen D); seg_backward; the two Adam updates.
+
+    One D forward serves each half.  With ImagePool(0) the reference's two
+    forwards of D on the GT predictions (trainer.py:1117 for the shape term,
+    :1127 for the pooled BCE term) see the same detached input and the same
+    weights, and so do its two on the no-GT predictions (:1097 with D frozen
+    for the generator's term, :1141 for D's own): D has no batch statistics and
+    no dropout, so each pair computes the same values, and the gradients the
+    reference accumulates over three backward calls are the sum formed here.
+
+    `losses` is [loss_seg, loss_adv, loss_D, loss_D_shape] (the reference's log
+    line; loss_D_shape unscaled).  `bad_rows` (device int32) counts the points
+    whose D output left [0, 1] in the last step: torch's BCELoss raises there,
+    a captured graph cannot, so the caller checks the counter when it reads the
+    losses.  Soft labels: explicit (soft_gt / soft_nogt, one per point) or
+    drawn on the device keyed by (seed, the generator's step counter, row), the
+    draws of SegAdvTrainStep for the same seed.  D always runs in f32."""
+
+    def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
+                 lambda_adv=0.01, lambda_disc_shape=1.0, lr=1e-4, lr_D=1e-4, betas=(0.9, 0.999),
+                 eps=1e-8, device="cuda", precision=None, seed=0, keep_activations=False):
+        from .discriminator import StackDiscNet
+        if not isinstance(model, PointNetSeg) or not isinstance(model_D, StackDiscNet):
+            raise TypeError("SegStackTrainStep: expected a PointNetSeg and a StackDiscNet")
+        if model_D.input_dim != model.output_dim:
+            raise ValueError(f"model_D takes {model_D.input_dim} channels, the generator predicts "
+                             f"{model.output_dim} classes")
+        if model_D.num_shapes < 16:
+            raise ValueError(f"model_D has {model_D.num_shapes} shape classes, cls is 16 wide")
+        super().__init__(model, (optimizer, optimizer_D), [(lr, betas, eps), (lr_D, betas, eps)],
+                         device, precision, keep_activations, model_D)
+        self.lambda_seg, self.lambda_adv = float(lambda_seg), float(lambda_adv)
+        self.lambda_disc_shape, self.seed = float(lambda_disc_shape), int(seed)
+        # [loss_seg, loss_adv, loss_D, loss_D's GT part, its no-GT part, loss_D_shape]
+        self.loss_buf = torch.zeros(6, device=self.device)
+        self.bad_buf = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self._loss_idx = torch.tensor([0, 1, 2, 5], device=self.device)  # the log line's order
+        self.d_out = None
+        self._ws = None
+
+    def __call__(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
+                 apply_adam=True):
+        self._run(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, apply_adam)
+        return self.losses
+
+    def _run(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, apply_adam):
+        from .discriminator import PWD_LOG_SOFTMAX, PWD_SOFTMAX, stackdisc_backward, \
+            stackdisc_forward, stackdisc_workspace
+        B, N, _ = pts_gt.shape
+        _check_dev(pts_gt, "pts_gt")
+        _check_dev(pts_nogt, "pts_nogt", shape=(B, N, 3))
+        if seg.shape != (B, N) or seg.dtype != torch.int64 or not seg.is_contiguous():
+            raise ValueError("seg: expected contiguous int64 (B, N)")
+        M = B * N
+        wpl = None
+        if _PLANES:  # every weight's planes (fp32 mode reads conv6's only)
+            _engine().split(self.param, self.wph, self.wpl)
+            wpl = self.wplanes
+        pts = torch.cat([pts_gt, pts_nogt])
+        cls_gt = cls_gt.float().reshape(B, 1, 16)
+        cls = torch.cat([cls_gt, cls_nogt.float().reshape(B, 1, 16)])
+        fw = seg_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
+        ncls = fw["dims"][2]
+        logits = fw["logits"]
+        d = torch.empty(2 * M, ncls, device=self.device)
+        ws = _ws(self.lib.pcadv_row_ce_workspace_bytes(M), self.device)
+        check(self.lib.pcadv_row_ce(_p(logits), ncls, _p(seg), M, ncls, self.lambda_seg,
+                                    _p(self.loss_buf), _p(d), _p(ws), ws.numel(), stream_ptr()),
+              "pcadv_row_ce")
+        if self._ws is None or self._ws[0] != M:
+            self._ws = (M, stackdisc_workspace(2 * M, self.device))
+        dws = self._ws[1]
+        # make_shape_label (utils/utils.py:33-38): one label per GT cloud
+        shape_label = torch.argmax(cls_gt.reshape(B, 16), dim=1).to(torch.int32)
+        m = torch.empty(2 * M, device=self.device)
+        d_out = torch.empty(2 * M, device=self.device)
+        argc = torch.empty(2 * M, device=self.device, dtype=torch.int32)
+        dm_d = torch.empty(2 * M, device=self.device)
+        dm_adv = torch.empty(M, device=self.device)
+        stackdisc_forward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, m, argc,
+                          d_out, dws, losses=self.loss_buf[1:6], shape_label=shape_label,
+                          pts_per_cloud=N, lambda_disc_shape=self.lambda_disc_shape,
+                          soft0=None if soft_gt is None else soft_gt.reshape(M),
+                          soft1=None if soft_nogt is None else soft_nogt.reshape(M),
+                          seed=self.seed, step_count=self.step_count, dm_d=dm_d, dm_adv=dm_adv,
+                          grads5=self.d_grad_views[8:10], bad_rows=self.bad_buf)
+        stackdisc_backward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, m,
+                           argc, dws, dm_d, self.d_grad_views, dm_adv=dm_adv,
+                           lambda_adv=self.lambda_adv, dlogits=d)
+        seg_backward(fw, d, None, out=self.grad_views)
+        if self.keep_activations:
+            self.fw, self.d_out = fw, d_out
+        if apply_adam:
+            self.adam()
+
+    def adam(self):
+        """optimizer.step() and optimizer_D.step() (trainer.py:1152-1153)."""
+        self._adam(0, self.lr, self.betas, self.eps)
+        self._adam(1, self.lr_D, self.betas_D, self.eps_D)
+
+    @property
+    def losses(self):
+        """[loss_seg, loss_adv, loss_D, loss_D_shape], the order of the reference's
+        log line (one gather from the loss buffer by a resident index: a new
+        tensor on every read)."""
+        return self.loss_buf.index_select(0, self._loss_idx)
+
+    @property
+    def bad_rows(self):
+        """The number of points whose D output was outside [0, 1] in the last
+        step (device int32)."""
+        return self.bad_buf[0]
+
+    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None):
+        """One HIP graph of a step reading the given resident buffers: a single
+        stream, no parallel branches (state is restored to what it was before
+        the warm-up)."""
+        def body():
+            self._run(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True)
         return self._capture(body, body)

@@ -26,7 +26,7 @@ from .pointnet import PointNetCls, feature_transform_regularizer
 from .dataset import gather_at_multi
 from .flat import capture_graphs
 from .step import AdvFtTrainStep, AdvTrainStep
-from .utils import make_D_label
+from .utils import make_D_label, make_shape_label
 
 
 def run_testing(dataloader, model, criterion, logger, test_iter, writer, args):
@@ -1168,12 +1168,21 @@ def run_training_pointnet_seg(trainloader_gt, trainloader_gt_iter, testloader, t
     return max_test_accu, max_test_cat_iou, max_test_all_iou
 
 
+def _plain_ce(loss):
+    return type(loss) is torch.nn.CrossEntropyLoss and loss.weight is None \
+        and loss.reduction == "mean" and loss.ignore_index < 0 and loss.label_smoothing == 0.0
+
+
 def _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, pool_gt, pool_nogt,
-                     args):
-    """The configuration SegAdvTrainStep implements (run_training_seg's fast path)."""
-    from .discriminator import PointwiseDiscNet
+                     args, shape_criterion=None):
+    """The configuration SegAdvTrainStep implements (run_training_seg's fast
+    path), or, with a shape_criterion, the one SegStackTrainStep implements
+    (run_training_seg_stack's: StackDiscNet, BCELoss, two plain CrossEntropyLoss)."""
+    from .discriminator import PointwiseDiscNet, StackDiscNet
     from .seg import PointNetSeg
-    if not (isinstance(model, PointNetSeg) and isinstance(model_D, PointwiseDiscNet)):
+    stack = shape_criterion is not None
+    if not (isinstance(model, PointNetSeg)
+            and isinstance(model_D, StackDiscNet if stack else PointwiseDiscNet)):
         return False
     if model_D.input_dim != model.output_dim or str(args.device).split(":")[0] != "cuda":
         return False
@@ -1183,12 +1192,15 @@ def _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
         g = opt.param_groups[0]
         if g.get("weight_decay", 0) or g.get("amsgrad") or g.get("maximize"):
             return False
-    if type(gan_loss) is not torch.nn.BCEWithLogitsLoss or gan_loss.weight is not None \
+    if stack:
+        if type(gan_loss) is not torch.nn.BCELoss or gan_loss.weight is not None \
+                or gan_loss.reduction != "mean" or not _plain_ce(shape_criterion) \
+                or model_D.num_shapes < 16:
+            return False
+    elif type(gan_loss) is not torch.nn.BCEWithLogitsLoss or gan_loss.weight is not None \
             or gan_loss.pos_weight is not None or gan_loss.reduction != "mean":
         return False
-    if type(seg_loss) is not torch.nn.CrossEntropyLoss or seg_loss.weight is not None \
-            or seg_loss.reduction != "mean" or seg_loss.ignore_index >= 0 \
-            or seg_loss.label_smoothing != 0.0:
+    if not _plain_ce(seg_loss):
         return False
     return getattr(pool_gt, "pool_size", 1) == 0 and getattr(pool_nogt, "pool_size", 1) == 0
 
@@ -1237,25 +1249,71 @@ def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, po
     return [l_seg.item(), loss_adv.item(), loss_semi_value, loss_D_value]
 
 
+def _seg_stack_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, shape_criterion,
+                    pool_gt, pool_nogt, pts, cls, seg, pts_nogt, cls_nogt, args):
+    """utils/trainer.py:1059-1153 through autograd over the same modules: returns
+    [loss_seg, loss_adv, loss_D, loss_D_shape].  gan_loss is applied to D's
+    probability output, so torch's own BCELoss range checks apply here."""
+    optimizer.zero_grad()
+    optimizer_D.zero_grad()
+    for param in model_D.parameters():  # train G
+        param.requires_grad = False
+    pred, _ = model(pts, cls)
+    l_seg = seg_loss(pred, seg)
+    pred_gt_softmax = F.softmax(pred, dim=1)
+    pred_nogt, _ = model(pts_nogt, cls_nogt)
+    pred_nogt_softmax = F.log_softmax(pred_nogt, dim=1)
+    _, D_out = model_D(pred_nogt_softmax)
+    loss_adv = gan_loss(D_out, make_D_label(input=D_out, value=1, device=args.device, random=False))
+    (args.lambda_seg * l_seg + args.lambda_adv * loss_adv).backward()
+    for param in model_D.parameters():  # train D
+        param.requires_grad = True
+    pred_gt_softmax = pred_gt_softmax.detach()
+    S_out_gt, _ = model_D(pred_gt_softmax)
+    shape = make_shape_label(input=cls.squeeze(1), npts=S_out_gt.shape[2])
+    loss_D_shape = shape_criterion(S_out_gt, shape)
+    (args.lambda_disc_shape * loss_D_shape).backward()
+    loss_D_value = 0.0
+    for pool, x, value in ((pool_gt, pred_gt_softmax, 1), (pool_nogt, pred_nogt_softmax, 0)):
+        _, D_out = model_D(pool.query(x.detach()))
+        loss_D = 0.5 * gan_loss(D_out, make_D_label(input=D_out, value=value, device=args.device,
+                                                    random=True))
+        loss_D.backward()
+        loss_D_value += loss_D.item()
+    optimizer.step()
+    optimizer_D.step()
+    return [l_seg.item(), loss_adv.item(), loss_D_value, loss_D_shape.item()]
+
+
 def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetloader_nogt_iter,
                   testloader, testdataset, model, model_D, gan_loss, seg_loss, optimizer,
                   optimizer_D, history_pool_gt, history_pool_nogt, train_logger, test_logger,
-                  writer, args, semi_loss=None):
-    """The iteration loop shared by run_training_seg (semi_loss None) and
-    run_training_seg_semi (pseudo-label term from iteration semi_start + 1).
+                  writer, args, semi_loss=None, shape_criterion=None):
+    """The iteration loop shared by run_training_seg (semi_loss None),
+    run_training_seg_semi (pseudo-label term from iteration semi_start + 1) and
+    run_training_seg_stack (shape_criterion given: StackDiscNet, BCELoss and
+    SegStackTrainStep take the places of PointwiseDiscNet, BCEWithLogitsLoss
+    and SegAdvTrainStep, with the stack loop's log line and tensorboard tags).
     With PointNetSeg + PointwiseDiscNet, two plain Adams, CrossEntropyLoss +
     BCEWithLogitsLoss and ImagePool(0) on the HIP device, every iteration whose
     two batches have the same shape is one SegAdvTrainStep; any other
     configuration, and a ragged last batch, runs the reference's body through
-    autograd over the same modules.  Where the two reference loops differ, so
-    do these: the fused step's condition, the log line, and the checkpoint by
-    accuracy that only the plain loop writes."""
-    from .seg import SegAdvTrainStep
-    with_semi = semi_loss is not None
+    autograd over the same modules.  With a shape_criterion the fused
+    configuration is instead PointNetSeg + StackDiscNet (at least 16 shape
+    classes), two plain Adams, plain CrossEntropyLoss for seg_loss and
+    shape_criterion, BCELoss (mean, no weight) and ImagePool(0): every
+    iteration with equal batch shapes is one SegStackTrainStep (any point
+    count: this D does not use input_pts), after which bad_rows > 0 raises
+    BCELoss's error; everything else runs _seg_stack_body (see
+    run_training_seg_stack).  Where the reference loops differ, so do these:
+    the fused step's condition, the log line, the tensorboard tags, and the
+    checkpoint by accuracy that the semi loop does not write."""
+    from .seg import SegAdvTrainStep, SegStackTrainStep
+    with_semi, stack = semi_loss is not None, shape_criterion is not None
     max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
     max_train_epoch = max_train_cat_epoch = max_train_all_epoch = 0
     fusable = _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                               history_pool_gt, history_pool_nogt, args) \
+                               history_pool_gt, history_pool_nogt, args, shape_criterion) \
         and (not with_semi or _semi_fusable(semi_loss))
     semi_args = dict(lambda_semi=float(getattr(args, "lambda_semi", 1.0)),
                      semi_th=float(getattr(args, "semi_TH", 0.8))) if with_semi else {}
@@ -1264,6 +1322,9 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
     if with_semi:
         line = ('iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} loss semi = {4:.3f} '
                 'loss_D = {5:.3f}')
+    elif stack:
+        line = ('iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} loss_D = {4:.3f} '
+                'loss_D_shape = {5:.3f} ')
     else:
         line = 'iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} loss_D = {4:.3f} '
 
@@ -1288,8 +1349,15 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
         # semi loop's mask indexes (B, N), as the reference's does
         if fusable and pts.shape == pts_nogt.shape and (
                 model_D.input_pts == pts.shape[1] if with_semi
-                else (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0):
-            if step is None:
+                else stack or (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0):
+            if step is None and stack:
+                step = SegStackTrainStep(model, model_D, optimizer=optimizer,
+                                         optimizer_D=optimizer_D, lambda_seg=args.lambda_seg,
+                                         lambda_adv=args.lambda_adv,
+                                         lambda_disc_shape=args.lambda_disc_shape,
+                                         device=args.device,
+                                         seed=int(getattr(args, "seed", 0) or 0))
+            elif step is None:
                 step = SegAdvTrainStep(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
                                        lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
                                        device=args.device, seed=int(getattr(args, "seed", 0) or 0),
@@ -1298,21 +1366,37 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
                 step.after_eager()
             eager_since = False
             step.sync_hyper()
-            step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
-                 cls_nogt.contiguous(), semi=semi)
-            vals = (step.losses_semi if with_semi else step.losses).tolist()
+            if stack:
+                step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
+                     cls_nogt.contiguous())
+                vals = step.losses.tolist()
+                if int(step.bad_rows.item()) > 0:  # what BCELoss raises in the eager body
+                    raise RuntimeError("all elements of input should be between 0 and 1")
+            else:
+                step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
+                     cls_nogt.contiguous(), semi=semi)
+                vals = (step.losses_semi if with_semi else step.losses).tolist()
         else:
             if step is not None:
                 step.sync_optimizer_state()
             eager_since = True
-            vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                                 history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
-                                 cls_nogt, args, semi_loss=semi_loss, semi=semi)
+            if stack:
+                vals = _seg_stack_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                                       shape_criterion, history_pool_gt, history_pool_nogt, pts,
+                                       cls, seg, pts_nogt, cls_nogt, args)
+            else:
+                vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                                     history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
+                                     cls_nogt, args, semi_loss=semi_loss, semi=semi)
         train_logger.info(line.format(i_iter, args.total_iterations, *vals))
         if tb:
             writer.add_scalar('Loss/train_seg', vals[0], i_iter)
             writer.add_scalar('Loss/train_adv', vals[1], i_iter)
-            writer.add_scalar('Loss/train_disc', vals[-1], i_iter)
+            if stack:
+                writer.add_scalar('Loss/train_D', vals[2], i_iter)
+                writer.add_scalar('Loss/train_D_shape', vals[3], i_iter)
+            else:
+                writer.add_scalar('Loss/train_disc', vals[-1], i_iter)
         if i_iter % args.iter_test_epoch == 0:
             ep = i_iter // args.iter_test_epoch
             save("epoch_{}".format(ep))
@@ -1368,3 +1452,35 @@ def run_training_seg_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
                          targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
                          seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
                          train_logger, test_logger, writer, args, semi_loss=semi_loss)
+
+
+def run_training_seg_stack(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                           targetloader_nogt_iter, testloader, testdataset, model, model_D,
+                           gan_loss, seg_loss, shape_criterion, optimizer, optimizer_D,
+                           history_pool_gt, history_pool_nogt, train_logger, test_logger, writer,
+                           args):
+    """utils/trainer.py:1028-1216: adversarial segmentation with the stacked
+    shape discriminator (StackDiscNet): gan_loss = BCELoss on D's probability
+    output, plus args.lambda_disc_shape x shape_criterion(D's shape logits on
+    the GT clouds, each cloud's class), which trains D only and is logged
+    unscaled.  The log line, the tensorboard tags (Loss/train_seg | adv | D |
+    D_shape) and the checkpoints (epoch_{}, best, best_cat_iou, best_all_iou)
+    are the reference's.
+
+    With PointNetSeg + StackDiscNet, two plain Adams, plain CrossEntropyLoss
+    for seg_loss and shape_criterion, BCELoss (mean, no weight), both pools of
+    size 0 and the HIP device, every iteration whose two batches have the same
+    shape is one SegStackTrainStep; anything else runs the reference's body
+    through autograd over the same modules (_seg_stack_body), where torch's own
+    BCELoss checks apply.
+
+    A D output outside [0, 1] (a trained conv5 bias can push the logsumexp
+    below 0) makes BCELoss raise.  The fused step counts such points on the
+    device, and this loop raises RuntimeError("all elements of input should be
+    between 0 and 1") when it reads the iteration's losses for the log line.
+    The one difference from the eager body: that iteration's two Adam updates
+    have already run when the error is raised."""
+    return _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                         targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
+                         seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
+                         train_logger, test_logger, writer, args, shape_criterion=shape_criterion)

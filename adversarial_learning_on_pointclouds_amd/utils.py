@@ -1,4 +1,5 @@
-"""GAN glue with the interface of utils/utils.py:9-31 (make_logger, make_D_label)."""
+"""GAN glue with the interface of utils/utils.py:9-38 (make_logger, make_D_label,
+make_shape_label)."""
 from __future__ import annotations
 
 import logging
@@ -36,3 +37,10 @@ def make_D_label(input, value, device, random=False):
         return torch.full(shape, float(value), device=device)
     lo, hi = _SOFT_RANGE[value]
     return torch.empty(shape, device=device).uniform_(lo, hi)
+
+
+def make_shape_label(input, npts):
+    """The shape class of every point of each cloud (utils/utils.py:33-38):
+    `input` (B, num_shapes) one-hot (or scores) -> int64 (B, npts), each row the
+    argmax of its cloud repeated."""
+    return torch.argmax(input, dim=1, keepdim=True).repeat(1, npts).long()

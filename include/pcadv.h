@@ -743,6 +743,87 @@ int pcadv_row_semi_ce(const float* logits, int64_t ld, const float* d_out, int M
                       int32_t* labels_out, float* loss, int32_t* kept_out, void* workspace,
                       size_t workspace_bytes, hipStream_t stream);
 
+/* ---- StackDiscNet of run_training_seg_stack ----------------------------------
+ * (models/discriminator.py:139-175, utils/trainer.py:1028-1216.)
+ * Additions to ABI 11 (nothing existing changes).
+ *
+ * The layout of pcadv_pwdisc_args: logits [n0 + n1][ncls] (row stride ld,
+ * 2 <= ncls <= 64), rows [0, n0) through transform t0 and rows [n0, n0 + n1)
+ * through t1 (the reference: softmax and log_softmax, trainer.py:1082,1095).
+ * w[i] / b[i]: conv1..conv4 as there, and conv5 ([num_shapes][1], [num_shapes];
+ * 2 <= num_shapes <= 32).  The activations are LeakyReLU(0.2).
+ *
+ * pcadv_stackdisc_forward, one launch, per row:
+ *   m        = max over the 128 channels of lrelu(conv4(..lrelu(conv1(x)))),
+ *              exact f32 MFMAs in k order; argc its channel (first on ties),
+ *   S[s]     = w5[s] m + b5[s]          (shape_logits [n0 + n1][num_shapes], optional),
+ *   d_out    = out / (out + 1), out = logsumexp_s S (less the row maximum).
+ * With losses != NULL (5 floats) also, BCE as torch's binary_cross_entropy
+ * (-(y max(log x, -100) + (1 - y) max(log(1 - x), -100)), derivative
+ * (x - y) / max(x (1 - x), 1e-12), any real label y):
+ *   losses[0] = loss_adv = mean over the no-GT rows of BCE(d_out, 1),
+ *   losses[2] = 0.5 mean over the GT rows against soft labels of U(0.7, 1.05),
+ *   losses[3] = 0.5 mean over the no-GT rows against soft labels of U(0, 0.305),
+ *   losses[1] = loss_D = losses[2] + losses[3],
+ *   losses[4] = loss_D_shape = mean over the GT rows of CrossEntropy(S,
+ *               shape_label[row / pts_per_cloud]), unscaled,
+ *   dm_d[n0 + n1]  = d(loss_D + lambda_disc_shape loss_D_shape) / dm,
+ *   dm_adv[n1]     = d loss_adv / dm (optional),
+ *   dw[4] / db[4]  = conv5's gradients of loss_D + lambda_disc_shape loss_D_shape,
+ *   *bad_rows      = the number of rows whose d_out is not in [0, 1] (NaN
+ *                    included; torch's BCELoss raises there).  Written by every
+ *                    forward with losses; such rows' loss and derivative values
+ *                    are unspecified, and nothing faults.
+ * The soft labels are soft0 / soft1 or drawn with pcadv_pwdisc_forward's Philox
+ * keys (rng_seed, *step_count, row): the same labels for the same seed.  n0 must
+ * be a multiple of pts_per_cloud; shape_label holds n0 / pts_per_cloud int32
+ * (a label outside [0, num_shapes) selects no class).  All sums run in a fixed
+ * order.  The workspace's first 256 bytes are the ticket, as above.
+ *
+ * pcadv_stackdisc_backward, one launch and the fixed-order finish: recomputes
+ * x1..x3, routes a unit gradient from channel argc through the masks
+ * (y > 0 ? 1 : 0.2, the arg-max channel's own mask on m included; no row is
+ * dead) and writes dw[0..3] / db[0..3] = the gradients of sum_row dm_d[row]
+ * m[row], and with dlogits and dm_adv the gradient of lambda_adv sum_j
+ * dm_adv[j] m[n0 + j] through t1 into rows [n0, n0 + n1) of dlogits.  Reads m,
+ * argc; x_out as in pcadv_pwdisc_backward. */
+typedef struct pcadv_stackdisc_args {
+  const float* logits;
+  int64_t ld;
+  int ncls, n0, n1, t0, t1;
+  const float* w[5];
+  const float* b[5];
+  int num_shapes;
+  const int32_t* shape_label;
+  int pts_per_cloud;
+  float lambda_disc_shape;
+  float* m;
+  int32_t* argc;
+  float* d_out;
+  float* shape_logits;
+  float* losses;
+  const float* soft0;
+  const float* soft1;
+  float* soft_out;
+  uint64_t rng_seed;
+  const int32_t* step_count;
+  float* dm_d;
+  float* dm_adv;
+  int32_t* bad_rows;
+  float lambda_adv;
+  float* dw[5];
+  float* db[5];
+  float* dlogits;
+  int64_t ldd;
+  int max_workgroups;
+  void* workspace;
+  size_t workspace_bytes;
+  float* x_out;
+} pcadv_stackdisc_args;
+size_t pcadv_stackdisc_workspace_bytes(int64_t rows, int max_workgroups);
+int pcadv_stackdisc_forward(const pcadv_stackdisc_args* args, hipStream_t stream);
+int pcadv_stackdisc_backward(const pcadv_stackdisc_args* args, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

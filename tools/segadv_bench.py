@@ -18,6 +18,12 @@ are printed and written to profiles/segadv_bench.json.  Needs the MI355X.
 (semi=True, a threshold that keeps about half the no-GT points) against the
 same step without it, alternated the same way, into
 profiles/segadv_semi_bench.json.
+
+--stack times run_training_seg_stack's step (SegStackTrainStep with
+StackDiscNet(2048, 50, 16)) against the pointwise adversarial step and the
+generator-only step, three graphs on the same 32 clouds and equal generators,
+alternated the same way, with the two discriminators' launches alone, into
+profiles/segstack_bench.json.
 """
 import argparse
 import json
@@ -80,6 +86,94 @@ def _d_alone(step, M, steps):
         b.synchronize()
         res[name] = a.elapsed_time(b) / steps
     return res
+
+
+def _stack_d_alone(step, M, steps):
+    """_d_alone for the stacked discriminator's launches."""
+    from adversarial_learning_on_pointclouds_amd import discriminator as D
+    dev = step.device
+    lg = torch.randn(2 * M, 50, device=dev) * 2
+    m, d_out = torch.empty(2 * M, device=dev), torch.empty(2 * M, device=dev)
+    argc = torch.empty(2 * M, device=dev, dtype=torch.int32)
+    dd, da = torch.empty(2 * M, device=dev), torch.empty(M, device=dev)
+    dl, ws = torch.empty(2 * M, 50, device=dev), D.stackdisc_workspace(2 * M, dev)
+    losses, bad = torch.zeros(5, device=dev), torch.zeros(1, device=dev, dtype=torch.int32)
+    labels = torch.zeros(M // 2048, device=dev, dtype=torch.int32)
+
+    def fwd():
+        D.stackdisc_forward(lg, 50, M, M, D.PWD_SOFTMAX, D.PWD_LOG_SOFTMAX, step.d_params, m, argc,
+                            d_out, ws, losses=losses, shape_label=labels, pts_per_cloud=2048,
+                            lambda_disc_shape=1.0, seed=1, step_count=step.step_count, dm_d=dd,
+                            dm_adv=da, grads5=step.d_grad_views[8:10], bad_rows=bad)
+
+    def bwd():
+        D.stackdisc_backward(lg, 50, M, M, D.PWD_SOFTMAX, D.PWD_LOG_SOFTMAX, step.d_params, m, argc,
+                             ws, dd, step.d_grad_views, dm_adv=da, lambda_adv=0.01, dlogits=dl)
+    res = {}
+    for name, fn in (("d_forward_ms", fwd), ("d_backward_ms", bwd)):
+        fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(steps):
+            fn()
+        b.record()
+        b.synchronize()
+        res[name] = a.elapsed_time(b) / steps
+    return res
+
+
+def _stack(a):
+    """--stack: SegStackTrainStep against SegAdvTrainStep and SegTrainStep."""
+    import adversarial_learning_on_pointclouds_amd as pc
+    B, N = 16, 2048
+    rng = np.random.default_rng(0)
+    torch.manual_seed(0)
+    pts, cls, seg = _inputs(rng, 2 * B, N)
+    gens = [pc.PointNetSeg(50).cuda() for _ in range(3)]
+    for g in gens[1:]:
+        g.load_state_dict(gens[0].state_dict())
+    stack = pc.SegStackTrainStep(gens[0], pc.StackDiscNet(N, 50, 16).cuda(), lr=1e-4, lr_D=1e-4,
+                                 lambda_adv=0.01, lambda_disc_shape=1.0, seed=5)
+    adv = pc.SegAdvTrainStep(gens[1], pc.PointwiseDiscNet(N, 50).cuda(), lr=1e-4, lr_D=1e-4,
+                             lambda_adv=0.01, seed=5)
+    sup = pc.SegTrainStep(gens[2], lr=1e-4)
+    halves = (pts[:B].contiguous(), cls[:B].contiguous(), seg[:B].contiguous(),
+              pts[B:].contiguous(), cls[B:].contiguous())
+    graphs = {"stack": stack.capture_on(*halves), "adv": adv.capture_on(*halves),
+              "seg": sup.capture_on(pts, cls, seg)}
+    for g in graphs.values():  # warm-up
+        _time(g, 5)
+    times = {k: [] for k in graphs}
+    for _ in range(a.rounds):
+        for k, g in graphs.items():
+            times[k].append(_time(g, a.steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    diffs = [s - p for s, p in zip(times["stack"], times["adv"])]
+    out = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "steps": a.steps,
+           "what": {"stack": "SegStackTrainStep B=16+16 N=2048 fp32, graph replay",
+                    "adv": "SegAdvTrainStep B=16+16 N=2048 fp32, graph replay",
+                    "seg": "SegTrainStep B=32 N=2048 fp32, graph replay"}}
+    for k in graphs:
+        out[k + "_ms"] = {"median": med[k], "min": min(times[k]), "max": max(times[k]),
+                          "rounds": times[k]}
+    out["stack_over_adv_us"] = {"median_of_medians": 1e3 * (med["stack"] - med["adv"]),
+                                "per_round": [1e3 * x for x in diffs],
+                                "median": 1e3 * statistics.median(diffs),
+                                "min": 1e3 * min(diffs), "max": 1e3 * max(diffs)}
+    out["round_spread_us"] = {k: 1e3 * (max(v) - min(v)) for k, v in times.items()}
+    out["d_cost_ms"] = {"stack": med["stack"] - med["seg"], "adv": med["adv"] - med["seg"]}
+    out["losses_last"] = [float(x) for x in stack.losses.tolist()]
+    out["bad_rows_last"] = int(stack.bad_rows.item())
+    out["d_alone"] = {"stack": _stack_d_alone(stack, B * N, a.steps),
+                      "adv": _d_alone(adv, B * N, a.steps)}
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"stack_ms": med["stack"], "adv_ms": med["adv"], "seg_ms": med["seg"],
+                      "stack_over_adv_us": out["stack_over_adv_us"]["median"],
+                      "round_spread_us": out["round_spread_us"], "d_alone": out["d_alone"]}))
 
 
 def _semi(a):
@@ -148,14 +242,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--semi", action="store_true",
                     help="time semi=True against semi=False (profiles/segadv_semi_bench.json)")
+    ap.add_argument("--stack", action="store_true",
+                    help="time SegStackTrainStep against both (profiles/segstack_bench.json)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join("profiles", "segadv_semi_bench.json" if a.semi else "segadv_bench.json")
+        a.out = os.path.join("profiles", "segadv_semi_bench.json" if a.semi else
+                             "segstack_bench.json" if a.stack else "segadv_bench.json")
     if not torch.cuda.is_available():
         sys.exit("segadv_bench: no HIP device (the steps are timed on the MI355X only)")
     if a.semi:
         return _semi(a)
+    if a.stack:
+        return _stack(a)
     import adversarial_learning_on_pointclouds_amd as pc
     B, N = 16, 2048
     rng = np.random.default_rng(0)
