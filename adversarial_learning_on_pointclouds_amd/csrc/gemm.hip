@@ -1673,7 +1673,14 @@ static int launch_gemm_impl(const float* a, long long lda, int ta, const float* 
     PC_HIP_CHECK_LAUNCH("k_gemm_small");
     return PCADV_OK;
   }
-  if (precise) {
+  // Three products leave up to 3 * 2^-16 = 4.6e-5 of each |a b| (the two
+  // operands' split residuals and the dropped lo lo term); the engine's
+  // ~1.2e-5 of sum|a b| holds because those errors average over the terms of
+  // a sum.  K < 16 has too few terms for that (2.8e-5 |a b| measured at
+  // K = 1) and no plane-form twin to stay bitwise with (pcadv_gemm_bf2 needs
+  // K % 16 == 0), and six products over half a k-tile cost nothing: it takes
+  // the precise form.
+  if (precise || K < 16) {
     if (ta == 0 && tb == 0) return accumulate ? gemm_launch<0, 0, 1, 6>(p, 1, s) : gemm_launch<0, 0, 0, 6>(p, 1, s);
     if (ta == 0 && tb == 1)
       return accumulate ? gemm_launch<0, 1, 1, 6>(p, 1, s, slot) : gemm_launch<0, 1, 0, 6>(p, 1, s, slot);
@@ -1866,6 +1873,8 @@ static int wgrad_prepare(const float* dz, long long ldz, const float* x, long lo
   j.w = wgrad_plan(rows, O, Kin, rows_per_group);
   PC_REQUIRE(ws && ws_bytes >= gemm_wgrad_workspace_bytes(rows, O, Kin, rows_per_group),
              "gemm_wgrad: workspace");
+  // the slabs are written and summed as 16-B vectors when Kin (or O * Kin) % 4 == 0
+  PC_REQUIRE(((uintptr_t)ws & 15) == 0, "gemm_wgrad: workspace must be 16-B aligned");
   j.slabs = static_cast<float*>(ws);
   j.csum = (db || gsum) ? j.slabs + (size_t)j.w.nz * O * Kin : nullptr;
   GemmP& p = j.p;
@@ -2057,6 +2066,8 @@ int launch_conv_max_x3(const float* x, long long ldx, int C, int Npts, int K, co
   PC_REQUIRE(x && w && gmax && gidx && C > 0 && Npts > 0 && K > 0 && O > 0,
              "conv_max_x3: bad shape");
   PC_REQUIRE(K % 32 == 0 && ldx % 4 == 0, "conv_max_x3: K %% 32 and ldx %% 4 required");
+  // k_max_combine re-evaluates the candidates with 16-B loads of x and w rows
+  PC_REQUIRE((((uintptr_t)x | (uintptr_t)w) & 15) == 0, "conv_max_x3: x and w must be 16-B aligned");
   PC_REQUIRE(ws && ws_bytes >= conv_max_x3_workspace_bytes(C, Npts, O), "conv_max_x3: workspace");
   PC_REQUIRE(fits31(Npts, ldx, 4) && fits31(Npts, ldxp, 2) && fits31(O, K, 4),
              "conv_max_x3: a cloud's rows and the weights must span < 2 GB");
@@ -2331,7 +2342,7 @@ k_cmx_dw(const float* __restrict__ g, const float* __restrict__ gmax,
       for (int t = 0; t < 4; ++t) acc[t] = fmaf(gv[u], v[u][t], acc[t]);
     }
   }
-  if (k < K) *reinterpret_cast<f32x4*>(dw + (size_t)o * K + k) = acc;
+  if (dw && k < K) *reinterpret_cast<f32x4*>(dw + (size_t)o * K + k) = acc;
   if (blockIdx.y == 0 && threadIdx.x == 0 && db) db[o] = sb;
 }
 
@@ -2499,9 +2510,12 @@ int launch_cmx_bwd(const float* g, const float* gmax, const int32_t* gidx, const
   PC_REQUIRE(g && gmax && gidx && x && w && C > 0 && Npts > 0 && O > 0 && O <= CMX_MAXO && K > 0 &&
                  O < 65536 && K % 4 == 0 && ldx % 4 == 0 && (!dx || (K <= CMX_MAXK && lddx % 4 == 0)),
              "cmx_bwd: bad shape C=%d N=%d O=%d K=%d", C, Npts, O, K);
-  if (dw) {
-    hipLaunchKernelGGL(k_cmx_dw, dim3(O, (K + 511) / 512), dim3(128), 0, s, g, gmax, gidx, x, ldx,
-                       C, Npts, O, K, dw, db);
+  // both kernels move x, w, dw and dx rows as 16-B vectors
+  PC_REQUIRE((((uintptr_t)x | (uintptr_t)w | (uintptr_t)dw | (uintptr_t)dx) & 15) == 0,
+             "cmx_bwd: x, w, dw and dx must be 16-B aligned");
+  if (dw || db) {  // db is formed by k_cmx_dw's first column block, with or without dw
+    hipLaunchKernelGGL(k_cmx_dw, dim3(O, dw ? (K + 511) / 512 : 1), dim3(128), 0, s, g, gmax, gidx,
+                       x, ldx, C, Npts, O, K, dw, db);
     PC_HIP_CHECK_LAUNCH("k_cmx_dw");
   }
   if (dx) {

@@ -268,7 +268,10 @@ int pcadv_linear_bwd(const float* dy, const float* y, int act,
  * (PointNetSeg, models/pointnet.py:261-317; run_training_pointnet_seg,
  * utils/trainer.py:310-400.)  Rows are points (point-major [B*N][C]); f32
  * operands are split to bf16 hi + lo and multiplied as three bf16 MFMA products
- * with f32 accumulation (relative error <= ~1.2e-5 of sum|a b|).
+ * with f32 accumulation (relative error <= ~1.2e-5 of sum|a b| over a sum
+ * whose terms' errors average out; one product alone can be off by up to
+ * 3 * 2^-16 = 4.6e-5 of |a b|, so reductions shorter than K = 16 always take
+ * the six-product form below).
  *
  * pcadv_gemm: C[m][n] (+)= sum_k A[m][k] B[n][k] (+ bias[n] + bias_rows[m /
  * rows_per_group][n]), ReLU optional.  A[m][k] = a[m*lda + k] (ta = 0) or
@@ -278,9 +281,19 @@ int pcadv_linear_bwd(const float* dy, const float* y, int act,
  * then zeroes C where cmask <= 0: the producer of a data gradient applies the
  * relu' of the layer below, so every consumer reads dZ = dY relu'(Y) already
  * masked.  precise = 1 multiplies six products of hi/mid/lo splits instead
- * (f32-level accuracy; the gradients).  c_hi / c_lo (nullable, bf16, row
+ * (f32-level accuracy; the gradients); K < 16 does so whatever precise says.  c_hi / c_lo (nullable, bf16, row
  * stride ldcp): the epilogue also writes C's hi / lo planes, the operand form
- * pcadv_gemm_bf2 stages without splitting. */
+ * pcadv_gemm_bf2 stages without splitting.
+ * Requirements: lda >= K (ta = 0) or M (ta = 1), ldb >= K (tb = 0) or N
+ * (tb = 1), ldc >= N, ldm >= N; float-aligned pointers, any stride and any
+ * N, K (16-B loads are used where an operand is 16-B aligned with a stride
+ * % 4 == 0 and no vector straddles an edge, dword loads elsewhere: the same
+ * values either way); bias [N] and bias_rows [ceil(M / rows_per_group)][N]
+ * dense; every operand spans < 2 GB.  Output planes need N % 4 == 0,
+ * ldcp >= N, ldcp % 4 == 0, 8-B aligned planes, and C, bias, bias_rows and
+ * cmask 16-B aligned with ldc % 4 == 0 and ldm % 4 == 0; they are not
+ * available on the few-row form (ta = 0, M <= 32: exact f32 FMAs on the
+ * vector ALUs instead of MFMAs, the same epilogue). */
 int pcadv_gemm(const float* a, int64_t lda, int ta, const float* b, int64_t ldb, int tb,
                float* c, int64_t ldc, int M, int N, int K, const float* bias,
                const float* bias_rows, int rows_per_group, int relu, int accumulate,
@@ -291,7 +304,8 @@ int pcadv_gemm(const float* a, int64_t lda, int ta, const float* b, int64_t ldb,
  * B [N][K], the 2-way splits of f32 matrices made once by their producers:
  * hi = bf16(v), lo = bf16(v - hi)); bitwise the result pcadv_gemm computes
  * from the f32 matrices (precise = 0), without re-splitting every tile.
- * K % 16, lda % 8, ldb % 8, 16-B aligned planes. */
+ * K % 16, lda % 8, ldb % 8, lda >= K, ldb >= K, 16-B aligned planes (any M,
+ * N; row strides above K allowed); the output planes as for pcadv_gemm. */
 int pcadv_gemm_bf2(const void* a_hi, const void* a_lo, int64_t lda, const void* b_hi,
                    const void* b_lo, int64_t ldb, float* c, int64_t ldc, void* c_hi, void* c_lo,
                    int64_t ldcp, int M, int N, int K, const float* bias, const float* bias_rows,
@@ -308,7 +322,9 @@ int pcadv_split_bf2(const float* x, int64_t ld, int rows, int cols, void* hi, vo
  * each group of rows_per_group rows ([rows / rows_per_group][O], overwritten:
  * fc1's per-cloud sums).  Both come from the staged dz, no second pass.
  * rows_per_group (0 = one group) also sets the slab plan, so pass the same
- * value to the workspace query. */
+ * value to the workspace query.  ldz >= O, ldx >= Kin, ldo >= Kin, any
+ * alignment of dz and x; the workspace 16-B aligned; db and gsum each may be
+ * NULL; accumulate applies to dw and db. */
 size_t pcadv_gemm_wgrad_workspace_bytes(int rows, int O, int Kin, int rows_per_group);
 int pcadv_gemm_wgrad(const float* dz, int64_t ldz, const float* x, int64_t ldx, int rows, int O,
                      int Kin, float* dw, int64_t ldo, float* db, float* gsum, int rows_per_group,
@@ -335,7 +351,8 @@ typedef struct pcadv_gemm_desc {
  * enqueues the GEMM g (a data gradient: pcadv_gemm's arguments), and where both
  * have the engine's pairable forms (g: ta = 0, tb = 1, either precision, M > 32,
  * operands vectorisable: 16-B aligned rows, VEC >= 2) the two run as ONE launch, their workgroups side by side, each output bitwise its
- * own launch's.  g must neither read nor write anything w reads or writes.
+ * own launch's; a g of another form is enqueued on its own.  g must not write
+ * anything w reads or writes, nor read anything w writes (both may read the same dz).
  * pcadv_wgrad_finish then enqueues the remaining dw (and db) sums of n such
  * weight gradients in one launch (more launches above 16).  Between the two
  * calls the caller keeps dw, db and the workspaces alive and untouched; nothing
@@ -352,7 +369,9 @@ int pcadv_wgrad_small(const float* s, int64_t lds, int B, int O, const float* x0
                       int64_t ldo, int accumulate, hipStream_t stream);
 
 /* Column sums (bias gradients): out[n] (+)= sum_m x[m][n] [ymask[m][n] > 0];
- * pcadv_group_colsum writes one row of sums per rows_per_group rows. */
+ * pcadv_group_colsum writes one row of sums per rows_per_group rows (M %
+ * rows_per_group == 0; out [M / rows_per_group][N] dense, overwritten).
+ * ymask nullable; ld, ldm >= N, any alignment. */
 size_t pcadv_colsum_workspace_bytes(int M, int N);
 int pcadv_colsum(const float* x, const float* ymask, int64_t ld, int64_t ldm, int M, int N,
                  float* out, int accumulate, void* workspace, size_t workspace_bytes,
@@ -364,22 +383,28 @@ int pcadv_group_colsum(const float* x, const float* ymask, int64_t ld, int64_t l
  * global max, pointnet.py:301-303): gmax [C][O], gidx [C][O] (first index on
  * ties of the f32 values; with relu the pooled value is relu(max)).  A screened
  * GEMM keeps per-128-point-tile top-2 candidates; the winner (and the
- * runner-up on near-ties) is re-evaluated as an f32 dot product of x and w. */
+ * runner-up on near-ties) is re-evaluated as an f32 dot product of x and w.
+ * K % 32 == 0, ldx % 4 == 0, ldx >= K, x and w ([O][K] dense) 16-B aligned;
+ * any C, Npts, O; b nullable. */
 size_t pcadv_conv_max_x3_workspace_bytes(int C, int Npts, int O);
 int pcadv_conv_max_x3(const float* x, int64_t ldx, int C, int Npts, int K, const float* w,
                       const float* b, int O, int relu, float* gmax, int32_t* gidx,
                       void* workspace, size_t workspace_bytes, hipStream_t stream);
 /* The same with the screened GEMM staging x and w from their bf16 hi / lo
- * planes (x still given in f32 for the exact re-evaluation). */
+ * planes (x still given in f32 for the exact re-evaluation): ldxp % 8 == 0,
+ * ldxp >= K, w's planes [O][K] dense, all four planes 16-B aligned. */
 int pcadv_conv_max_bf2(const float* x, int64_t ldx, const void* x_hi, const void* x_lo,
                        int64_t ldxp, int C, int Npts, int K, const float* w, const void* w_hi,
                        const void* w_lo, const float* b, int O, int relu, float* gmax,
                        int32_t* gidx, void* workspace, size_t workspace_bytes,
                        hipStream_t stream);
 /* Its backward: g' = dgmax [gmax > 0]; dw [O][K] and db [O] overwritten
- * (nullable), dx rows (stride lddx, nullable, K <= 512) accumulated:
- * deterministic.  relu_x = 1 masks the dx additions by [x > 0] (x the output
- * of a ReLU layer: the gradient leaves already multiplied by its relu'). */
+ * (each nullable on its own: db is formed with or without dw), dx rows
+ * (stride lddx, nullable, K <= 512) accumulated: deterministic.  relu_x = 1
+ * masks the dx additions by [x > 0] (x the output of a ReLU layer: the
+ * gradient leaves already multiplied by its relu').  K % 4 == 0, ldx % 4 == 0,
+ * lddx % 4 == 0, O <= 4096, gidx in [0, Npts); x, w, dw ([O][K] dense) and dx
+ * 16-B aligned. */
 int pcadv_conv_max_x3_bwd(const float* dgmax, const float* gmax, const int32_t* gidx,
                           const float* x, int64_t ldx, int C, int Npts, int O, int K,
                           const float* w, float* dw, float* db, float* dx, int64_t lddx,
@@ -465,7 +490,9 @@ int pcadv_iter_epilogue(int32_t* counters, int ncounters, const float* losses, i
                         float* ring, int slots, int32_t* ring_count, hipStream_t stream);
 
 /* CrossEntropyLoss over rows (the per-point segmentation loss, mean over M
- * points): *loss, and dlogits = scale * dL/dlogits (same stride ld). */
+ * points): *loss, and dlogits = scale * dL/dlogits (same stride ld >= ncls;
+ * the padding columns are not written).  Any M and ncls; labels in [0, ncls);
+ * the row maximum is subtracted before the exponentials. */
 size_t pcadv_row_ce_workspace_bytes(int M);
 int pcadv_row_ce(const float* logits, int64_t ld, const int64_t* labels, int M, int ncls,
                  float scale, float* loss, float* dlogits, void* workspace,

@@ -118,6 +118,32 @@ def test_gather_multi_and_epilogue_refuse_bad_arguments():
     assert b"loss ring" in lib.pcadv_last_error()
 
 
+def test_gemm_engine_refuses_misaligned_vector_operands():
+    """The operands the dense GEMM engine always moves as 16-B vectors must be
+    16-B aligned (include/pcadv.h): x and w of the conv + max and of its
+    backward, that backward's dw and dx, the weight gradient's workspace.  A
+    pointer one float off is refused on the host, before any launch."""
+    import ctypes
+    from adversarial_learning_on_pointclouds_amd import _lib
+    lib = _lib.load()
+    al, off = (lambda k: ctypes.c_void_p(0x100000 * k)), (lambda k: ctypes.c_void_p(0x100000 * k + 4))
+    C, Npts, K, O = 2, 64, 32, 16
+    nb = lib.pcadv_conv_max_x3_workspace_bytes(C, Npts, O)
+    for x, w in ((off(1), al(2)), (al(1), off(2))):
+        assert lib.pcadv_conv_max_x3(x, K, C, Npts, K, w, None, O, 1, al(3), al(4), al(5), nb, None) == -1
+        assert b"16-B aligned" in lib.pcadv_last_error()
+    for bad in range(4):  # x, w, dw, dx
+        x, w, dw, dx = [off(k) if k - 4 == bad else al(k) for k in range(4, 8)]
+        assert lib.pcadv_conv_max_x3_bwd(al(1), al(2), al(3), x, K, C, Npts, O, K, w, dw, al(9), dx, K,
+                                         0, None) == -1
+        assert b"16-B aligned" in lib.pcadv_last_error()
+    rows, Kin = 128, 8
+    nb = lib.pcadv_gemm_wgrad_workspace_bytes(rows, O, Kin, 0)
+    assert lib.pcadv_gemm_wgrad(al(1), O, al(2), Kin, rows, O, Kin, al(3), Kin, None, None, 0, 0, off(4),
+                                nb + 64, None) == -1
+    assert b"workspace must be 16-B aligned" in lib.pcadv_last_error()
+
+
 def test_image_pool_history_vs_reference_g10():
     """ImagePool(3) over six queries on a seeded Python RNG returns what the
     reference's utils/image_pool.py:26-55 returned (fixture g10)."""
