@@ -17,6 +17,7 @@
 // logsumexp, out / (out + 1), the BCE and shape terms and conv5's gradients
 // behind the channel max (second half of this file).
 #include <cmath>
+#include <type_traits>
 
 #include "common.h"
 
@@ -831,11 +832,42 @@ int pwd_grid(int ntiles, int max_wg, int dflt) {
   const int cap = max_wg > 0 ? max_wg : dflt;
   return ntiles < cap ? ntiles : cap;
 }
-size_t pwd_partial_bytes(int ntiles) { return ((size_t)ntiles * 3 * 4 + 255) / 256 * 256; }
 
-int pwd_check(const pcadv_pwdisc_args* a, const char* what, PwdNet& p) {
+// The workspace of either discriminator: the ticket alone on its line, the
+// forward's partial sums (pwdisc: three per tile; stackdisc: SK_NP per forward
+// workgroup), then one weight-gradient slab per backward workgroup.
+struct PwdWs {
+  size_t partial_bytes, bytes;
+  unsigned* ticket(void* ws) const { return reinterpret_cast<unsigned*>(ws); }
+  float* partial(void* ws) const {
+    return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + WS_HEAD);
+  }
+  float* slabs(void* ws) const {
+    return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + WS_HEAD + partial_bytes);
+  }
+};
+PwdWs pwd_ws(long long rows, int max_wg, bool stack) {
+  if (rows < 1) return {0, 0};
+  const int nt = pwd_tiles(rows);
+  const size_t np = stack ? (size_t)pwd_grid(nt, max_wg, PD_FWD_WG) * SK_NP : (size_t)nt * 3;
+  const size_t pb = (np * 4 + 255) / 256 * 256;
+  return {pb, WS_HEAD + pb + (size_t)pwd_grid(nt, max_wg, PD_BWD_WG) * SL_N * 4};
+}
+
+float* pwd_row_out(const pcadv_pwdisc_args* a) { return a->out; }
+float* pwd_row_out(const pcadv_stackdisc_args* a) { return a->m; }
+
+// The fields the two args structs share.  pcadv_stackdisc_args adds num_shapes
+// and conv5, whose [S][1] weight is read by scalars (no alignment asked).
+template <typename A>
+int pwd_check(const A* a, const char* what, PwdNet& p) {
+  constexpr bool STACK = std::is_same_v<A, pcadv_stackdisc_args>;
+  constexpr int NL = STACK ? 5 : 4;
   PC_REQUIRE(a, "%s: args is NULL", what);
   PC_REQUIRE(a->ncls >= 2 && a->ncls <= 64, "%s: ncls = %d, expected 2..64", what, a->ncls);
+  if constexpr (STACK)
+    PC_REQUIRE(a->num_shapes >= 2 && a->num_shapes <= SK_MAXS,
+               "%s: num_shapes = %d, expected 2..%d", what, a->num_shapes, SK_MAXS);
   PC_REQUIRE(a->n0 >= 0 && a->n1 >= 0 && (long long)a->n0 + a->n1 >= 1 &&
                  (long long)a->n0 + a->n1 <= 0x7fffffffLL - PD_ROWS,
              "%s: row counts n0 = %d, n1 = %d", what, a->n0, a->n1);
@@ -845,13 +877,16 @@ int pwd_check(const pcadv_pwdisc_args* a, const char* what, PwdNet& p) {
              "%s: transforms (%d, %d): PCADV_PWD_NONE / _SOFTMAX / _LOG_SOFTMAX", what, a->t0,
              a->t1);
   PC_REQUIRE(a->max_workgroups >= 0, "%s: max_workgroups = %d", what, a->max_workgroups);
-  PC_REQUIRE(a->logits && a->out && a->argc, "%s: logits, out and argc are required", what);
-  for (int i = 0; i < 4; ++i) {
+  PC_REQUIRE(a->logits && pwd_row_out(a) && a->argc, "%s: logits, %s and argc are required", what,
+             STACK ? "m" : "out");
+  for (int i = 0; i < NL; ++i) {
     PC_REQUIRE(a->w[i] && a->b[i], "%s: conv%d's weight and bias are required", what, i + 1);
-    PC_REQUIRE(i == 0 || ((uintptr_t)a->w[i] & 15) == 0, "%s: conv%d's weight is not 16-B aligned",
-               what, i + 1);
-    p.w[i] = a->w[i];
-    p.b[i] = a->b[i];
+    PC_REQUIRE(i == 0 || i == 4 || ((uintptr_t)a->w[i] & 15) == 0,
+               "%s: conv%d's weight is not 16-B aligned", what, i + 1);
+    if (i < 4) {
+      p.w[i] = a->w[i];
+      p.b[i] = a->b[i];
+    }
   }
   p.logits = a->logits;
   p.ld = a->ld;
@@ -874,29 +909,73 @@ int pwd_lds(K kernel, size_t bytes, const char* what) {
   return PCADV_OK;
 }
 
+// What a forward with losses asks of either struct beyond its own outputs:
+// a step counter for drawn labels and the workspace.
+template <typename A>
+int pwd_check_losses(const A* a, const char* what, const PwdWs& ws) {
+  const bool drawn = (a->n0 > 0 && !a->soft0) || (a->n1 > 0 && !a->soft1);
+  PC_REQUIRE(!drawn || a->step_count, "%s: device-drawn labels need step_count", what);
+  PC_REQUIRE(a->workspace && a->workspace_bytes >= ws.bytes, "%s: workspace of %zu bytes, need %zu",
+             what, a->workspace_bytes, ws.bytes);
+  return PCADV_OK;
+}
+
+// The backward of both: k_pwd_bwd<ACT> on b (its slabs set here) and the
+// fixed-order finish into a's dw[0..3] / db[0..3].
+template <int ACT, typename A>
+int pwd_launch_bwd(const A* a, const char* what, const PwdNet& p, PwdBwdArgs b, const PwdWs& ws,
+                   hipStream_t s) {
+  constexpr const char* kname = ACT == ACT_RELU ? "k_pwd_bwd" : "k_pwd_bwd<lrelu>";
+  PwdGrads g;
+  for (int i = 0; i < 4; ++i) {
+    PC_REQUIRE(a->dw[i] && a->db[i], "%s: conv%d's gradients are required", what, i + 1);
+    g.dw[i] = a->dw[i];
+    g.db[i] = a->db[i];
+  }
+  PC_REQUIRE(!a->dlogits || a->ldd >= a->ncls, "%s: dlogits stride %lld < ncls", what,
+             (long long)a->ldd);
+  PC_REQUIRE(a->workspace && a->workspace_bytes >= ws.bytes, "%s: workspace of %zu bytes, need %zu",
+             what, a->workspace_bytes, ws.bytes);
+  b.argc = a->argc;
+  b.lambda_adv = a->lambda_adv;
+  b.dlogits = a->dlogits;
+  b.ldd = a->ldd;
+  b.x_out = a->x_out;
+  b.slabs = ws.slabs(a->workspace);
+  // one guard per instantiation, i.e. per kernel; see launch_pwdisc_fwd
+  static int once = pwd_lds(k_pwd_bwd<ACT>, sizeof(PwdBwdLds), kname);
+  if (once) return once;
+  const int nt = pwd_tiles((long long)p.n0 + p.n1);
+  const int grid = pwd_grid(nt, a->max_workgroups, PD_BWD_WG);
+  hipLaunchKernelGGL(k_pwd_bwd<ACT>, dim3(grid), dim3(PD_T), sizeof(PwdBwdLds), s, p, b, nt);
+  PC_HIP_CHECK_LAUNCH(kname);
+  hipLaunchKernelGGL(k_pwd_bwd_finish, dim3((SL_N + 255) / 256), dim3(256), 0, s, b.slabs, grid,
+                     a->ncls, g);
+  PC_HIP_CHECK_LAUNCH("k_pwd_bwd_finish");
+  return PCADV_OK;
+}
+
 }  // namespace
 
 size_t pwdisc_workspace_bytes(long long rows, int max_wg) {
-  if (rows < 1) return 0;
-  const int nt = pwd_tiles(rows);
-  return WS_HEAD + pwd_partial_bytes(nt) + (size_t)pwd_grid(nt, max_wg, PD_BWD_WG) * SL_N * 4;
+  return pwd_ws(rows, max_wg, false).bytes;
+}
+size_t stackdisc_workspace_bytes(long long rows, int max_wg) {
+  return pwd_ws(rows, max_wg, true).bytes;
 }
 
 int launch_pwdisc_fwd(const pcadv_pwdisc_args* a, hipStream_t s) {
+  const char* what = "pcadv_pwdisc_forward";
   PwdNet p;
-  if (int rc = pwd_check(a, "pcadv_pwdisc_forward", p)) return rc;
-  const long long rows = (long long)a->n0 + a->n1;
-  const int nt = pwd_tiles(rows);
+  if (int rc = pwd_check(a, what, p)) return rc;
+  const int nt = pwd_tiles((long long)a->n0 + a->n1);
   PwdFwdOut o = {};
   o.out = a->out;
   o.argc = a->argc;
   if (a->losses) {
-    PC_REQUIRE(a->dout_d, "pcadv_pwdisc_forward: losses need dout_d");
-    const bool drawn = (a->n0 > 0 && !a->soft0) || (a->n1 > 0 && !a->soft1);
-    PC_REQUIRE(!drawn || a->step_count, "pcadv_pwdisc_forward: device-drawn labels need step_count");
-    PC_REQUIRE(a->workspace && a->workspace_bytes >= pwdisc_workspace_bytes(rows, a->max_workgroups),
-               "pcadv_pwdisc_forward: workspace of %zu bytes, need %zu", a->workspace_bytes,
-               pwdisc_workspace_bytes(rows, a->max_workgroups));
+    const PwdWs ws = pwd_ws((long long)a->n0 + a->n1, a->max_workgroups, false);
+    PC_REQUIRE(a->dout_d, "%s: losses need dout_d", what);
+    if (int rc = pwd_check_losses(a, what, ws)) return rc;
     o.losses = a->losses;
     o.soft0 = a->soft0;
     o.soft1 = a->soft1;
@@ -905,8 +984,8 @@ int launch_pwdisc_fwd(const pcadv_pwdisc_args* a, hipStream_t s) {
     o.step = a->step_count;
     o.dout_d = a->dout_d;
     o.dout_adv = a->dout_adv;
-    o.ticket = reinterpret_cast<unsigned*>(a->workspace);
-    o.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + WS_HEAD);
+    o.ticket = ws.ticket(a->workspace);
+    o.partial = ws.partial(a->workspace);
   }
   // Once per process, as every launcher of this library does (set outside any
   // stream capture by the first eager call).  The attribute belongs to the
@@ -921,105 +1000,23 @@ int launch_pwdisc_fwd(const pcadv_pwdisc_args* a, hipStream_t s) {
 }
 
 int launch_pwdisc_bwd(const pcadv_pwdisc_args* a, hipStream_t s) {
+  const char* what = "pcadv_pwdisc_backward";
   PwdNet p;
-  if (int rc = pwd_check(a, "pcadv_pwdisc_backward", p)) return rc;
-  const long long rows = (long long)a->n0 + a->n1;
-  const int nt = pwd_tiles(rows);
-  PC_REQUIRE(a->dout_d, "pcadv_pwdisc_backward: dout_d is required");
-  PwdGrads g;
-  for (int i = 0; i < 4; ++i) {
-    PC_REQUIRE(a->dw[i] && a->db[i], "pcadv_pwdisc_backward: conv%d's gradients are required", i + 1);
-    g.dw[i] = a->dw[i];
-    g.db[i] = a->db[i];
-  }
-  PC_REQUIRE(!a->dlogits || a->ldd >= a->ncls, "pcadv_pwdisc_backward: dlogits stride %lld < ncls",
-             (long long)a->ldd);
-  PC_REQUIRE(a->workspace && a->workspace_bytes >= pwdisc_workspace_bytes(rows, a->max_workgroups),
-             "pcadv_pwdisc_backward: workspace of %zu bytes, need %zu", a->workspace_bytes,
-             pwdisc_workspace_bytes(rows, a->max_workgroups));
+  if (int rc = pwd_check(a, what, p)) return rc;
+  PC_REQUIRE(a->dout_d, "%s: dout_d is required", what);
   PwdBwdArgs b;
   b.out = a->out;
-  b.argc = a->argc;
   b.dout_d = a->dout_d;
   b.dout_adv = a->dout_adv;
-  b.lambda_adv = a->lambda_adv;
-  b.dlogits = a->dlogits;
-  b.ldd = a->ldd;
-  b.x_out = a->x_out;
-  b.slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + WS_HEAD +
-                                     pwd_partial_bytes(nt));
-  static int once = pwd_lds(k_pwd_bwd<ACT_RELU>, sizeof(PwdBwdLds), "k_pwd_bwd");  // see launch_pwdisc_fwd
-  if (once) return once;
-  const int grid = pwd_grid(nt, a->max_workgroups, PD_BWD_WG);
-  hipLaunchKernelGGL(k_pwd_bwd<ACT_RELU>, dim3(grid), dim3(PD_T), sizeof(PwdBwdLds), s, p, b, nt);
-  PC_HIP_CHECK_LAUNCH("k_pwd_bwd");
-  hipLaunchKernelGGL(k_pwd_bwd_finish, dim3((SL_N + 255) / 256), dim3(256), 0, s, b.slabs, grid,
-                     a->ncls, g);
-  PC_HIP_CHECK_LAUNCH("k_pwd_bwd_finish");
-  return PCADV_OK;
-}
-
-}  // namespace pcadv
-
-// ---------------------------------------------------------------------------
-// StackDiscNet: host side
-// ---------------------------------------------------------------------------
-namespace pcadv {
-
-namespace {
-
-size_t stk_partial_bytes(int grid) { return ((size_t)grid * SK_NP * 4 + 255) / 256 * 256; }
-
-int stk_check(const pcadv_stackdisc_args* a, const char* what, PwdNet& p) {
-  PC_REQUIRE(a, "%s: args is NULL", what);
-  PC_REQUIRE(a->ncls >= 2 && a->ncls <= 64, "%s: ncls = %d, expected 2..64", what, a->ncls);
-  PC_REQUIRE(a->num_shapes >= 2 && a->num_shapes <= SK_MAXS, "%s: num_shapes = %d, expected 2..%d",
-             what, a->num_shapes, SK_MAXS);
-  PC_REQUIRE(a->n0 >= 0 && a->n1 >= 0 && (long long)a->n0 + a->n1 >= 1 &&
-                 (long long)a->n0 + a->n1 <= 0x7fffffffLL - PD_ROWS,
-             "%s: row counts n0 = %d, n1 = %d", what, a->n0, a->n1);
-  PC_REQUIRE(a->ld >= a->ncls, "%s: row stride ld = %lld < ncls = %d", what, (long long)a->ld,
-             a->ncls);
-  PC_REQUIRE(a->t0 >= 0 && a->t0 <= 2 && a->t1 >= 0 && a->t1 <= 2,
-             "%s: transforms (%d, %d): PCADV_PWD_NONE / _SOFTMAX / _LOG_SOFTMAX", what, a->t0,
-             a->t1);
-  PC_REQUIRE(a->max_workgroups >= 0, "%s: max_workgroups = %d", what, a->max_workgroups);
-  PC_REQUIRE(a->logits && a->m && a->argc, "%s: logits, m and argc are required", what);
-  for (int i = 0; i < 5; ++i) {
-    PC_REQUIRE(a->w[i] && a->b[i], "%s: conv%d's weight and bias are required", what, i + 1);
-    PC_REQUIRE(i == 0 || i == 4 || ((uintptr_t)a->w[i] & 15) == 0,
-               "%s: conv%d's weight is not 16-B aligned", what, i + 1);
-    if (i < 4) {
-      p.w[i] = a->w[i];
-      p.b[i] = a->b[i];
-    }
-  }
-  p.logits = a->logits;
-  p.ld = a->ld;
-  p.ncls = a->ncls;
-  p.n0 = a->n0;
-  p.n1 = a->n1;
-  p.t0 = a->t0;
-  p.t1 = a->t1;
-  return PCADV_OK;
-}
-
-}  // namespace
-
-size_t stackdisc_workspace_bytes(long long rows, int max_wg) {
-  if (rows < 1) return 0;
-  const int nt = pwd_tiles(rows);
-  return WS_HEAD + stk_partial_bytes(pwd_grid(nt, max_wg, PD_FWD_WG)) +
-         (size_t)pwd_grid(nt, max_wg, PD_BWD_WG) * SL_N * 4;
+  return pwd_launch_bwd<ACT_RELU>(a, what, p, b,
+                                  pwd_ws((long long)a->n0 + a->n1, a->max_workgroups, false), s);
 }
 
 int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, hipStream_t s) {
   const char* what = "pcadv_stackdisc_forward";
   PwdNet p;
-  if (int rc = stk_check(a, what, p)) return rc;
-  const long long rows = (long long)a->n0 + a->n1;
-  const int nt = pwd_tiles(rows);
-  const int grid = pwd_grid(nt, a->max_workgroups, PD_FWD_WG);
+  if (int rc = pwd_check(a, what, p)) return rc;
+  const int nt = pwd_tiles((long long)a->n0 + a->n1);
   PC_REQUIRE(a->d_out, "%s: d_out is required", what);
   StkFwdOut o = {};
   o.w5 = a->w[4];
@@ -1031,6 +1028,7 @@ int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, hipStream_t s) {
   o.shape_logits = a->shape_logits;
   o.ppc = 1;
   if (a->losses) {
+    const PwdWs ws = pwd_ws((long long)a->n0 + a->n1, a->max_workgroups, true);
     PC_REQUIRE(a->dm_d && a->dw[4] && a->db[4] && a->bad_rows,
                "%s: losses need dm_d, conv5's dw / db and bad_rows", what);
     if (a->n0 > 0) {
@@ -1039,12 +1037,7 @@ int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, hipStream_t s) {
                  what, a->pts_per_cloud, a->n0);
       o.ppc = a->pts_per_cloud;
     }
-    const bool drawn = (a->n0 > 0 && !a->soft0) || (a->n1 > 0 && !a->soft1);
-    PC_REQUIRE(!drawn || a->step_count, "%s: device-drawn labels need step_count", what);
-    PC_REQUIRE(a->workspace &&
-                   a->workspace_bytes >= stackdisc_workspace_bytes(rows, a->max_workgroups),
-               "%s: workspace of %zu bytes, need %zu", what, a->workspace_bytes,
-               stackdisc_workspace_bytes(rows, a->max_workgroups));
+    if (int rc = pwd_check_losses(a, what, ws)) return rc;
     o.shape_label = a->shape_label;
     o.lambda_shape = a->lambda_disc_shape;
     o.losses = a->losses;
@@ -1058,12 +1051,13 @@ int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, hipStream_t s) {
     o.dw5 = a->dw[4];
     o.db5 = a->db[4];
     o.bad_rows = a->bad_rows;
-    o.ticket = reinterpret_cast<unsigned*>(a->workspace);
-    o.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + WS_HEAD);
+    o.ticket = ws.ticket(a->workspace);
+    o.partial = ws.partial(a->workspace);
   }
   static int once = pwd_lds(k_stk_fwd, sizeof(PwdFwdLds), "k_stk_fwd");  // see launch_pwdisc_fwd
   if (once) return once;
-  hipLaunchKernelGGL(k_stk_fwd, dim3(grid), dim3(PD_T), sizeof(PwdFwdLds), s, p, o, nt);
+  hipLaunchKernelGGL(k_stk_fwd, dim3(pwd_grid(nt, a->max_workgroups, PD_FWD_WG)), dim3(PD_T),
+                     sizeof(PwdFwdLds), s, p, o, nt);
   PC_HIP_CHECK_LAUNCH("k_stk_fwd");
   return PCADV_OK;
 }
@@ -1071,43 +1065,14 @@ int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, hipStream_t s) {
 int launch_stackdisc_bwd(const pcadv_stackdisc_args* a, hipStream_t s) {
   const char* what = "pcadv_stackdisc_backward";
   PwdNet p;
-  if (int rc = stk_check(a, what, p)) return rc;
-  const long long rows = (long long)a->n0 + a->n1;
-  const int nt = pwd_tiles(rows);
+  if (int rc = pwd_check(a, what, p)) return rc;
   PC_REQUIRE(a->dm_d, "%s: dm_d is required", what);
-  PwdGrads g;
-  for (int i = 0; i < 4; ++i) {
-    PC_REQUIRE(a->dw[i] && a->db[i], "%s: conv%d's gradients are required", what, i + 1);
-    g.dw[i] = a->dw[i];
-    g.db[i] = a->db[i];
-  }
-  PC_REQUIRE(!a->dlogits || a->ldd >= a->ncls, "%s: dlogits stride %lld < ncls", what,
-             (long long)a->ldd);
-  PC_REQUIRE(a->workspace &&
-                 a->workspace_bytes >= stackdisc_workspace_bytes(rows, a->max_workgroups),
-             "%s: workspace of %zu bytes, need %zu", what, a->workspace_bytes,
-             stackdisc_workspace_bytes(rows, a->max_workgroups));
   PwdBwdArgs b;
   b.out = a->m;
-  b.argc = a->argc;
   b.dout_d = a->dm_d;
   b.dout_adv = a->dm_adv;
-  b.lambda_adv = a->lambda_adv;
-  b.dlogits = a->dlogits;
-  b.ldd = a->ldd;
-  b.x_out = a->x_out;
-  b.slabs = reinterpret_cast<float*>(
-      reinterpret_cast<char*>(a->workspace) + WS_HEAD +
-      stk_partial_bytes(pwd_grid(nt, a->max_workgroups, PD_FWD_WG)));
-  static int once = pwd_lds(k_pwd_bwd<ACT_LRELU>, sizeof(PwdBwdLds), "k_pwd_bwd<lrelu>");
-  if (once) return once;
-  const int grid = pwd_grid(nt, a->max_workgroups, PD_BWD_WG);
-  hipLaunchKernelGGL(k_pwd_bwd<ACT_LRELU>, dim3(grid), dim3(PD_T), sizeof(PwdBwdLds), s, p, b, nt);
-  PC_HIP_CHECK_LAUNCH("k_pwd_bwd<lrelu>");
-  hipLaunchKernelGGL(k_pwd_bwd_finish, dim3((SL_N + 255) / 256), dim3(256), 0, s, b.slabs, grid,
-                     a->ncls, g);
-  PC_HIP_CHECK_LAUNCH("k_pwd_bwd_finish");
-  return PCADV_OK;
+  return pwd_launch_bwd<ACT_LRELU>(a, what, p, b,
+                                   pwd_ws((long long)a->n0 + a->n1, a->max_workgroups, true), s);
 }
 
 }  // namespace pcadv

@@ -65,15 +65,46 @@ def _f32(t, name, numel=None):
     return t
 
 
+def _i32(t, name, numel):
+    if t.dtype != torch.int32 or t.numel() != numel or t.device.type != "cuda" \
+            or not t.is_contiguous():
+        raise TypeError(f"{name}: expected {numel} contiguous int32 on the HIP device")
+    return t
+
+
+# The two fused discriminators share their host path: one builder for the
+# common prefix of the two args structs, one backward and one workspace body.
+# What differs per net: the struct, the lengths of the parameters after conv1's
+# weight, and the struct's names for the per-row output and its two gradients.
+_PWD = ("pwdisc", _lib.PwdiscArgs, ("out", "dout_d", "dout_adv"))
+_STK = ("stackdisc", _lib.StackdiscArgs, ("m", "dm_d", "dm_adv"))
+_CONV_SIZES = (64, 4096, 64, 4096, 64, 8192, 128)  # conv1's bias .. conv4's bias
+
+
+def _workspace(net, rows, device, max_workgroups, zero):
+    n = getattr(_lib.load(), f"pcadv_{net[0]}_workspace_bytes")(int(rows), int(max_workgroups))
+    return (torch.zeros if zero else torch.empty)(max(int(n), 256), device=device,
+                                                  dtype=torch.uint8)
+
+
 def pwdisc_workspace(rows, device, max_workgroups=0, zero=True):
     """The workspace the forward and the backward of `rows` points share.  Only a
     forward with losses needs it zeroed (its ticket); the backward writes its
     slabs before it reads them, and a forward without losses takes ws=None."""
-    n = max(int(_lib.load().pcadv_pwdisc_workspace_bytes(int(rows), int(max_workgroups))), 256)
-    return (torch.zeros if zero else torch.empty)(n, device=device, dtype=torch.uint8)
+    return _workspace(_PWD, rows, device, max_workgroups, zero)
 
 
-def _args(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups):
+def stackdisc_workspace(rows, device, max_workgroups=0, zero=True):
+    """The workspace the stacked discriminator's forward and backward of `rows`
+    points share (zeroed once for the forward's ticket, as pwdisc_workspace)."""
+    return _workspace(_STK, rows, device, max_workgroups, zero)
+
+
+def _args(net, logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups):
+    """The args struct of `net` with everything the two structs share filled in:
+    logits, the row counts and transforms, conv1..'s parameters, the per-row
+    output, argc, max_workgroups and the workspace."""
+    _, struct, (out_name, _, _) = net
     rows = n0 + n1
     if logits.dim() != 2 or logits.shape[0] != rows or logits.shape[1] < ncls \
             or logits.stride(1) != 1:
@@ -83,26 +114,46 @@ def _args(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups):
         raise TypeError("logits: expected torch.float32 on the HIP device")
     if not 2 <= ncls <= PWD_MAX_DIM:
         raise ValueError(f"ncls: the fused discriminator takes 2..{PWD_MAX_DIM} channels, got {ncls}")
-    shapes = [(64, ncls), (64,), (64, 64), (64,), (64, 64), (64,), (128, 64), (128,)]
-    a = _lib.PwdiscArgs()
-    for i, (p, shp) in enumerate(zip(params, shapes)):
-        n = 1
-        for d in shp:
-            n *= d
-        _f32(p, f"D parameter {i}", n)
-        if i % 2 == 0:
-            a.w[i // 2] = p.data_ptr()
-        else:
-            a.b[i // 2] = p.data_ptr()
+    sizes = (64 * ncls,) + _CONV_SIZES
+    a = struct()
+    if net is _STK:
+        if len(params) != 10:
+            raise ValueError("params: expected conv1..conv5's weights and biases (10 tensors)")
+        a.num_shapes = S = params[9].numel()
+        if not 2 <= S <= STACK_MAX_SHAPES:
+            raise ValueError(f"num_shapes: the fused discriminator takes 2..{STACK_MAX_SHAPES}, got {S}")
+        sizes += (S, S)
+    for i, (p, n) in enumerate(zip(params, sizes)):
+        (a.b if i % 2 else a.w)[i // 2] = _f32(p, f"D parameter {i}", n).data_ptr()
     a.logits, a.ld = _vp(logits), logits.stride(0) if rows > 1 else max(logits.stride(0), ncls)
     a.ncls, a.n0, a.n1, a.t0, a.t1 = ncls, n0, n1, int(t0), int(t1)
-    a.out, a.argc = _vp(_f32(out, "out", rows)), _vp(argc)
-    if argc.dtype != torch.int32 or argc.numel() != rows or argc.device.type != "cuda":
-        raise TypeError("argc: expected int32 of one element per row on the HIP device")
+    setattr(a, out_name, _vp(_f32(out, out_name, rows)))
+    a.argc = _vp(_i32(argc, "argc", rows))
     a.max_workgroups = int(max_workgroups)
     if ws is not None:
         a.workspace, a.workspace_bytes = _vp(ws), ws.numel()
     return a
+
+
+def _backward(net, logits, ncls, n0, n1, t0, t1, params, out, argc, ws, d_d, grads, d_adv,
+              lambda_adv, dlogits, max_workgroups, x_out):
+    name, _, (_, d_name, adv_name) = net
+    a = _args(net, logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups)
+    setattr(a, d_name, _vp(_f32(d_d, d_name, n0 + n1)))
+    setattr(a, adv_name, _vp(None if d_adv is None else _f32(d_adv, adv_name, n1)))
+    a.lambda_adv = float(lambda_adv)
+    for i, (g, p) in enumerate(zip(grads[:8], params[:8])):
+        (a.db if i % 2 else a.dw)[i // 2] = _f32(g, f"D gradient {i}", p.numel()).data_ptr()
+    if x_out is not None:
+        a.x_out = _vp(_f32(x_out, "x_out", 3 * (n0 + n1) * 64))
+    if dlogits is not None:
+        if dlogits.dim() != 2 or dlogits.shape[0] != n0 + n1 or dlogits.shape[1] < ncls \
+                or dlogits.stride(1) != 1 or dlogits.dtype != torch.float32 \
+                or dlogits.device.type != "cuda":
+            raise ValueError("dlogits: expected point-major float32 rows like logits")
+        a.dlogits, a.ldd = _vp(dlogits), max(dlogits.stride(0), ncls)
+    entry = f"pcadv_{name}_backward"
+    check(getattr(_lib.load(), entry)(ctypes.byref(a), stream_ptr()), entry)
 
 
 def pwdisc_forward(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, *, losses=None,
@@ -110,7 +161,7 @@ def pwdisc_forward(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, *, losse
                    dout_adv=None, max_workgroups=0):
     """pcadv_pwdisc_forward on the current stream (include/pcadv.h): out, argc
     and, with `losses` (4 floats), the BCE terms with dout_d / dout_adv."""
-    a = _args(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups)
+    a = _args(_PWD, logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups)
     if losses is not None:
         a.losses = _vp(_f32(losses, "losses", 4))
         a.soft0 = _vp(None if soft0 is None else _f32(soft0, "soft0", n0))
@@ -129,150 +180,8 @@ def pwdisc_backward(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, dout_d,
     parameter-shaped tensors, state_dict order) are written, and rows
     [n0, n0 + n1) of `dlogits` when it and dout_adv are given.  x_out
     (3, n0 + n1, 64), optional, receives the recomputed x1..x3."""
-    a = _args(logits, ncls, n0, n1, t0, t1, params, out, argc, ws, max_workgroups)
-    a.dout_d = _vp(_f32(dout_d, "dout_d", n0 + n1))
-    a.dout_adv = _vp(None if dout_adv is None else _f32(dout_adv, "dout_adv", n1))
-    a.lambda_adv = float(lambda_adv)
-    for i, (g, p) in enumerate(zip(grads, params)):
-        _f32(g, f"D gradient {i}", p.numel())
-        if i % 2 == 0:
-            a.dw[i // 2] = g.data_ptr()
-        else:
-            a.db[i // 2] = g.data_ptr()
-    if x_out is not None:
-        a.x_out = _vp(_f32(x_out, "x_out", 3 * (n0 + n1) * 64))
-    if dlogits is not None:
-        if dlogits.dim() != 2 or dlogits.shape[0] != n0 + n1 or dlogits.shape[1] < ncls \
-                or dlogits.stride(1) != 1 or dlogits.dtype != torch.float32 \
-                or dlogits.device.type != "cuda":
-            raise ValueError("dlogits: expected point-major float32 rows like logits")
-        a.dlogits, a.ldd = _vp(dlogits), max(dlogits.stride(0), ncls)
-    check(_lib.load().pcadv_pwdisc_backward(ctypes.byref(a), stream_ptr()), "pcadv_pwdisc_backward")
-
-
-def _point_major(x):
-    """x (B, C, N) as point-major rows (B * N, ld) without a copy when it is a
-    permuted view of point-major storage (what PointNetSeg.forward returns)."""
-    B, C, N = x.shape
-    xt = x.permute(0, 2, 1)  # (B, N, C)
-    if not xt.is_contiguous():
-        xt = xt.contiguous()
-    return xt.reshape(B * N, C)
-
-
-class _PointwiseDisc(torch.autograd.Function):
-    """x (B, C, N) -> (B * N,) logits: the fused forward, and the fused backward
-    scaled per row by the incoming gradient."""
-
-    @staticmethod
-    def forward(ctx, x, *params):
-        B, C, N = x.shape
-        rows = _point_major(x.detach())
-        M = B * N
-        out = torch.empty(M, device=x.device)
-        argc = torch.empty(M, device=x.device, dtype=torch.int32)
-        ps = [p.detach().contiguous() for p in params]
-        pwdisc_forward(rows, C, 0, M, PWD_NONE, PWD_NONE, ps, out, argc, None)
-        ctx.save_for_backward(rows, out, argc, *ps)
-        ctx.dims = (B, C, N)
-        ctx.mark_non_differentiable(argc)
-        return out, argc
-
-    @staticmethod
-    def backward(ctx, dout, _dargc):
-        rows, out, argc, *ps = ctx.saved_tensors
-        B, C, N = ctx.dims
-        M = B * N
-        d = dout.reshape(M).contiguous().float()
-        grads = [torch.empty_like(p) for p in ps]
-        need_dx = ctx.needs_input_grad[0]
-        dl = torch.empty(M, C, device=rows.device) if need_dx else None
-        ws = pwdisc_workspace(M, rows.device, zero=False)
-        pwdisc_backward(rows, C, 0, M, PWD_NONE, PWD_NONE, ps, out, argc, ws, d, grads,
-                        dout_adv=d if need_dx else None, lambda_adv=1.0, dlogits=dl)
-        dx = dl.view(B, N, C).permute(0, 2, 1) if need_dx else None
-        return (dx, *grads)
-
-
-class PointwiseDiscNet(nn.Module):
-    """models/discriminator.py:53-79.  forward(x: B x input_dim x N) ->
-    B*N/input_pts x input_pts (B x N when N == input_pts)."""
-
-    def __init__(self, input_pts, input_dim):
-        super().__init__()
-        if not 2 <= int(input_dim) <= PWD_MAX_DIM:
-            raise ValueError(f"input_dim: the fused discriminator takes 2..{PWD_MAX_DIM} "
-                             f"channels, got {input_dim}")
-        if int(input_pts) < 1:
-            raise ValueError(f"input_pts: expected a positive point count, got {input_pts}")
-        self.input_pts = int(input_pts)
-        self.input_dim = int(input_dim)
-        self.conv1 = nn.Conv1d(input_dim, 64, 1)
-        self.conv2 = nn.Conv1d(64, 64, 1)
-        self.conv3 = nn.Conv1d(64, 64, 1)
-        self.conv4 = nn.Conv1d(64, 128, 1)
-
-    def check_input(self, x):
-        if x.dim() != 3 or x.shape[1] != self.input_dim:
-            raise ValueError(f"x: expected B x {self.input_dim} x N, got {tuple(x.shape)}")
-        if (x.shape[0] * x.shape[2]) % self.input_pts:
-            raise ValueError(f"x: {x.shape[0]} x {x.shape[2]} points do not fill rows of "
-                             f"input_pts = {self.input_pts}")
-        if not x.is_floating_point() or x.dtype != torch.float32:
-            raise TypeError(f"x: expected torch.float32, got {x.dtype}")
-
-    def forward(self, x):
-        self.check_input(x)
-        if x.device.type != "cuda":
-            raise ValueError(f"x: pcadv ops run on the HIP device only (got {x.device})")
-        out, _ = _PointwiseDisc.apply(x, *[p for _, p in self.named_parameters()])
-        return out.view(-1, self.input_pts)
-
-
-def stackdisc_workspace(rows, device, max_workgroups=0, zero=True):
-    """The workspace the stacked discriminator's forward and backward of `rows`
-    points share (zeroed once for the forward's ticket, as pwdisc_workspace)."""
-    n = max(int(_lib.load().pcadv_stackdisc_workspace_bytes(int(rows), int(max_workgroups))), 256)
-    return (torch.zeros if zero else torch.empty)(n, device=device, dtype=torch.uint8)
-
-
-def _i32(t, name, numel):
-    if t.dtype != torch.int32 or t.numel() != numel or t.device.type != "cuda" \
-            or not t.is_contiguous():
-        raise TypeError(f"{name}: expected {numel} contiguous int32 on the HIP device")
-    return t
-
-
-def _stack_args(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, max_workgroups):
-    rows = n0 + n1
-    if logits.dim() != 2 or logits.shape[0] != rows or logits.shape[1] < ncls \
-            or logits.stride(1) != 1:
-        raise ValueError(f"logits: expected point-major ({rows}, >= {ncls}) rows, "
-                         f"got {tuple(logits.shape)} with strides {logits.stride()}")
-    if logits.device.type != "cuda" or logits.dtype != torch.float32:
-        raise TypeError("logits: expected torch.float32 on the HIP device")
-    if not 2 <= ncls <= PWD_MAX_DIM:
-        raise ValueError(f"ncls: the fused discriminator takes 2..{PWD_MAX_DIM} channels, got {ncls}")
-    if len(params) != 10:
-        raise ValueError("params: expected conv1..conv5's weights and biases (10 tensors)")
-    S = params[9].numel()
-    if not 2 <= S <= STACK_MAX_SHAPES:
-        raise ValueError(f"num_shapes: the fused discriminator takes 2..{STACK_MAX_SHAPES}, got {S}")
-    shapes = [64 * ncls, 64, 4096, 64, 4096, 64, 8192, 128, S, S]
-    a = _lib.StackdiscArgs()
-    for i, (p, n) in enumerate(zip(params, shapes)):
-        _f32(p, f"D parameter {i}", n)
-        if i % 2 == 0:
-            a.w[i // 2] = p.data_ptr()
-        else:
-            a.b[i // 2] = p.data_ptr()
-    a.logits, a.ld = _vp(logits), logits.stride(0) if rows > 1 else max(logits.stride(0), ncls)
-    a.ncls, a.n0, a.n1, a.t0, a.t1, a.num_shapes = ncls, n0, n1, int(t0), int(t1), S
-    a.m, a.argc = _vp(_f32(m, "m", rows)), _vp(_i32(argc, "argc", rows))
-    a.max_workgroups = int(max_workgroups)
-    if ws is not None:
-        a.workspace, a.workspace_bytes = _vp(ws), ws.numel()
-    return a, S
+    _backward(_PWD, logits, ncls, n0, n1, t0, t1, params, out, argc, ws, dout_d, grads, dout_adv,
+              lambda_adv, dlogits, max_workgroups, x_out)
 
 
 def stackdisc_forward(logits, ncls, n0, n1, t0, t1, params, m, argc, d_out, ws, *,
@@ -284,7 +193,8 @@ def stackdisc_forward(logits, ncls, n0, n1, t0, t1, params, m, argc, d_out, ws, 
     d_out, optionally shape_logits (rows, num_shapes), and, with `losses` (5
     floats), the BCE and shape terms with dm_d / dm_adv, conv5's gradients
     grads5 = (dw5, db5) and the int32 bad_rows counter."""
-    a, S = _stack_args(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, max_workgroups)
+    a = _args(_STK, logits, ncls, n0, n1, t0, t1, params, m, argc, ws, max_workgroups)
+    S = a.num_shapes
     a.d_out = _vp(_f32(d_out, "d_out", n0 + n1))
     if shape_logits is not None:
         a.shape_logits = _vp(_f32(shape_logits, "shape_logits", (n0 + n1) * S))
@@ -316,26 +226,58 @@ def stackdisc_backward(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, dm_d, 
     `grads` (conv1..conv4, state_dict order) are written, and rows
     [n0, n0 + n1) of `dlogits` when it and dm_adv are given.  x_out
     (3, n0 + n1, 64), optional, receives the recomputed x1..x3."""
-    a, _ = _stack_args(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, max_workgroups)
-    a.dm_d = _vp(_f32(dm_d, "dm_d", n0 + n1))
-    a.dm_adv = _vp(None if dm_adv is None else _f32(dm_adv, "dm_adv", n1))
-    a.lambda_adv = float(lambda_adv)
-    for i, (g, p) in enumerate(zip(grads[:8], params[:8])):
-        _f32(g, f"D gradient {i}", p.numel())
-        if i % 2 == 0:
-            a.dw[i // 2] = g.data_ptr()
-        else:
-            a.db[i // 2] = g.data_ptr()
-    if x_out is not None:
-        a.x_out = _vp(_f32(x_out, "x_out", 3 * (n0 + n1) * 64))
-    if dlogits is not None:
-        if dlogits.dim() != 2 or dlogits.shape[0] != n0 + n1 or dlogits.shape[1] < ncls \
-                or dlogits.stride(1) != 1 or dlogits.dtype != torch.float32 \
-                or dlogits.device.type != "cuda":
-            raise ValueError("dlogits: expected point-major float32 rows like logits")
-        a.dlogits, a.ldd = _vp(dlogits), max(dlogits.stride(0), ncls)
-    check(_lib.load().pcadv_stackdisc_backward(ctypes.byref(a), stream_ptr()),
-          "pcadv_stackdisc_backward")
+    _backward(_STK, logits, ncls, n0, n1, t0, t1, params, m, argc, ws, dm_d, grads, dm_adv,
+              lambda_adv, dlogits, max_workgroups, x_out)
+
+
+def _point_major(x):
+    """x (B, C, N) as point-major rows (B * N, ld) without a copy when it is a
+    permuted view of point-major storage (what PointNetSeg.forward returns)."""
+    B, C, N = x.shape
+    xt = x.permute(0, 2, 1)  # (B, N, C)
+    if not xt.is_contiguous():
+        xt = xt.contiguous()
+    return xt.reshape(B * N, C)
+
+
+def _autograd_backward(net, ctx, dout):
+    """The backward of both autograd nodes: the fused backward scaled per row by
+    the incoming gradient.  Returns (dx, conv1..conv4's gradients)."""
+    rows, out, argc, *ps = ctx.saved_tensors
+    B, C, N = ctx.dims
+    M = B * N
+    d = dout.reshape(M).contiguous().float()
+    grads = [torch.empty_like(p) for p in ps[:8]]
+    need_dx = ctx.needs_input_grad[0]
+    dl = torch.empty(M, C, device=rows.device) if need_dx else None
+    ws = _workspace(net, M, rows.device, 0, zero=False)
+    _backward(net, rows, C, 0, M, PWD_NONE, PWD_NONE, ps, out, argc, ws, d, grads,
+              d if need_dx else None, 1.0, dl, 0, None)
+    dx = dl.view(B, N, C).permute(0, 2, 1) if need_dx else None
+    return (dx, *grads)
+
+
+class _PointwiseDisc(torch.autograd.Function):
+    """x (B, C, N) -> (B * N,) logits: the fused forward, and the fused backward
+    scaled per row by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        B, C, N = x.shape
+        rows = _point_major(x.detach())
+        M = B * N
+        out = torch.empty(M, device=x.device)
+        argc = torch.empty(M, device=x.device, dtype=torch.int32)
+        ps = [p.detach().contiguous() for p in params]
+        pwdisc_forward(rows, C, 0, M, PWD_NONE, PWD_NONE, ps, out, argc, None)
+        ctx.save_for_backward(rows, out, argc, *ps)
+        ctx.dims = (B, C, N)
+        ctx.mark_non_differentiable(argc)
+        return out, argc
+
+    @staticmethod
+    def backward(ctx, dout, _dargc):
+        return _autograd_backward(_PWD, ctx, dout)
 
 
 class _StackDiscMax(torch.autograd.Function):
@@ -362,55 +304,70 @@ class _StackDiscMax(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dm):
-        rows, m, argc, *ps = ctx.saved_tensors
-        B, C, N = ctx.dims
-        M = B * N
-        d = dm.reshape(M).contiguous().float()
-        grads = [torch.empty_like(p) for p in ps[:8]]
-        need_dx = ctx.needs_input_grad[0]
-        dl = torch.empty(M, C, device=rows.device) if need_dx else None
-        ws = stackdisc_workspace(M, rows.device, zero=False)
-        stackdisc_backward(rows, C, 0, M, PWD_NONE, PWD_NONE, ps, m, argc, ws, d, grads,
-                           dm_adv=d if need_dx else None, lambda_adv=1.0, dlogits=dl)
-        dx = dl.view(B, N, C).permute(0, 2, 1) if need_dx else None
-        return (dx, *grads, None, None)  # conv5 acts after this node
+        return (*_autograd_backward(_STK, ctx, dm), None, None)  # conv5 acts after this node
 
 
-class StackDiscNet(nn.Module):
-    """models/discriminator.py:139-175.  forward(x: B x input_dim x N) ->
-    (shape_logits B x num_shapes x N, disc_out B x N x 1)."""
+class _FusedDiscNet(nn.Module):
+    """What the two fused discriminators share: conv1..conv4 (ncls -> 64 -> 64
+    -> 64 -> 128, registered first and in this order, so the state_dicts are the
+    reference's) and the checks of the constructor's ranges and of the input."""
+    fills_rows = False  # PointwiseDiscNet: B * N must fill rows of input_pts
 
-    def __init__(self, input_pts, input_dim, num_shapes):
+    def __init__(self, input_pts, input_dim):
         super().__init__()
         if not 2 <= int(input_dim) <= PWD_MAX_DIM:
             raise ValueError(f"input_dim: the fused discriminator takes 2..{PWD_MAX_DIM} "
                              f"channels, got {input_dim}")
-        if not 2 <= int(num_shapes) <= STACK_MAX_SHAPES:
-            raise ValueError(f"num_shapes: the fused discriminator takes 2..{STACK_MAX_SHAPES} "
-                             f"shape classes, got {num_shapes}")
         if int(input_pts) < 1:
             raise ValueError(f"input_pts: expected a positive point count, got {input_pts}")
         self.input_pts = int(input_pts)
         self.input_dim = int(input_dim)
-        self.num_shapes = int(num_shapes)
         self.conv1 = nn.Conv1d(input_dim, 64, 1)
         self.conv2 = nn.Conv1d(64, 64, 1)
         self.conv3 = nn.Conv1d(64, 64, 1)
         self.conv4 = nn.Conv1d(64, 128, 1)
-        self.conv5 = nn.Conv1d(1, num_shapes, 1)
 
     def check_input(self, x):
         if x.dim() != 3 or x.shape[1] != self.input_dim:
             raise ValueError(f"x: expected B x {self.input_dim} x N, got {tuple(x.shape)}")
+        if self.fills_rows and (x.shape[0] * x.shape[2]) % self.input_pts:
+            raise ValueError(f"x: {x.shape[0]} x {x.shape[2]} points do not fill rows of "
+                             f"input_pts = {self.input_pts}")
         if not x.is_floating_point() or x.dtype != torch.float32:
             raise TypeError(f"x: expected torch.float32, got {x.dtype}")
 
-    def forward(self, x):
+    def _apply_fused(self, fn, x):
         self.check_input(x)
         if x.device.type != "cuda":
             raise ValueError(f"x: pcadv ops run on the HIP device only (got {x.device})")
+        return fn.apply(x, *[p for _, p in self.named_parameters()])
+
+
+class PointwiseDiscNet(_FusedDiscNet):
+    """models/discriminator.py:53-79.  forward(x: B x input_dim x N) ->
+    B*N/input_pts x input_pts (B x N when N == input_pts)."""
+    fills_rows = True
+
+    def forward(self, x):
+        out, _ = self._apply_fused(_PointwiseDisc, x)
+        return out.view(-1, self.input_pts)
+
+
+class StackDiscNet(_FusedDiscNet):
+    """models/discriminator.py:139-175.  forward(x: B x input_dim x N) ->
+    (shape_logits B x num_shapes x N, disc_out B x N x 1)."""
+
+    def __init__(self, input_pts, input_dim, num_shapes):
+        super().__init__(input_pts, input_dim)
+        if not 2 <= int(num_shapes) <= STACK_MAX_SHAPES:
+            raise ValueError(f"num_shapes: the fused discriminator takes 2..{STACK_MAX_SHAPES} "
+                             f"shape classes, got {num_shapes}")
+        self.num_shapes = int(num_shapes)
+        self.conv5 = nn.Conv1d(1, num_shapes, 1)
+
+    def forward(self, x):
+        m = self._apply_fused(_StackDiscMax, x)
         B, _, N = x.shape
-        m = _StackDiscMax.apply(x, *[p for _, p in self.named_parameters()])
         shape_logits = self.conv5(m.view(B, 1, N))  # B x S x N
         out = torch.logsumexp(shape_logits.transpose(2, 1), dim=2, keepdim=True)
         return shape_logits, out / (out + 1.0)

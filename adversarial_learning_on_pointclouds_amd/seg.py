@@ -37,6 +37,9 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, stream_ptr
+from .discriminator import (PWD_LOG_SOFTMAX, PWD_SOFTMAX, PointwiseDiscNet, StackDiscNet,
+                            pwdisc_backward, pwdisc_forward, pwdisc_workspace, stackdisc_backward,
+                            stackdisc_forward, stackdisc_workspace)
 from .flat import FlatAdam
 from .step import FusedStep
 
@@ -629,66 +632,62 @@ class SegTrainStep(_SegStep):
         return self.loss.view(1)
 
 
-class SegAdvTrainStep(_SegStep):
-    """One iteration of run_training_seg (utils/trainer.py:873-966) with
-    ImagePool(0), PointNetSeg + PointwiseDiscNet and two Adams, as native
-    launches on one stream, capturable into a HIP graph:
+class _SegDiscStep(_SegStep):
+    """What the two adversarial PointNetSeg steps share (SegAdvTrainStep with
+    PointwiseDiscNet, SegStackTrainStep with StackDiscNet): one iteration with
+    ImagePool(0) and two Adams as native launches on one stream, capturable
+    into a HIP graph:
 
       weight-plane split; seg_forward on the 2B clouds [GT; no-GT] (PointNetSeg
       has no batch statistics: the reference's two forwards); pcadv_row_ce on the
-      GT rows (dlogits rows [0, B N), scale lambda_seg); the fused D forward on
-      softmax(GT) / log_softmax(no-GT) (trainer.py:901,914) with loss_adv, loss_D
-      and their derivatives; the fused D backward (D's gradients from both of its
-      terms, and the no-GT rows of dlogits from lambda_adv loss_adv through the
-      frozen D); seg_backward; the two Adam updates.
+      GT rows (dlogits rows [0, B N), scale lambda_seg); the subclass's _disc:
+      the fused D forward on softmax(GT) / log_softmax(no-GT) with its losses
+      and their derivatives, and the fused D backward (D's gradients, and the
+      no-GT rows of dlogits from lambda_adv loss_adv through the frozen D);
+      seg_backward; the two Adam updates.
 
-    The no-GT rows feed the adversarial term and D's own term from one forward
-    (D is frozen in the first and its input detached in the second, so the three
-    reference forwards compute the same values).  Parameters, gradients and Adam
-    moments of G and of D are flat buffers handed to the torch modules and
-    optimizers as views.  D always runs in f32; `precision` is the generator's.
-    Soft labels: explicit (soft_gt / soft_nogt, one per point) or drawn on the
-    device keyed by (seed, the generator's step counter, row).
+    Parameters, gradients and Adam moments of G and of D are flat buffers handed
+    to the torch modules and optimizers as views.  D always runs in f32;
+    `precision` is the generator's.  Soft labels: explicit (soft_gt / soft_nogt,
+    one per point) or drawn on the device keyed by (seed, the generator's step
+    counter, row), the same draws in both steps for the same seed.
 
-    semi=True adds run_training_seg_semi's term (utils/trainer.py:1999-2024):
-    after the D backward, pcadv_row_semi_ce on the no-GT rows adds lambda_semi
-    times the cross entropy of the points whose D output is above semi_th
-    against their own argmax to those rows of dlogits (D receives nothing from
-    it).  It needs model_D.input_pts == N, as the reference's mask does.  The
-    term's loss and the number of kept points are `losses_semi[2]` and `kept`;
-    `losses` stays [loss_seg, loss_adv, loss_D].  A captured graph has `semi`
-    baked in: capture one graph per value."""
+    A subclass names its discriminator class and workspace function, implements
+    _disc and `losses`, and keeps its own terms in loss_buf[3:]."""
 
-    def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
-                 lambda_adv=0.01, lr=1e-4, lr_D=1e-4, betas=(0.9, 0.999), eps=1e-8, device="cuda",
-                 precision=None, seed=0, keep_activations=False, lambda_semi=1.0, semi_th=0.8):
-        from .discriminator import PointwiseDiscNet
-        if not isinstance(model, PointNetSeg) or not isinstance(model_D, PointwiseDiscNet):
-            raise TypeError("SegAdvTrainStep: expected a PointNetSeg and a PointwiseDiscNet")
+    _D_NET = _d_workspace = None
+
+    def __init__(self, model, model_D, optimizer, optimizer_D, lambda_seg, lambda_adv, lr, lr_D,
+                 betas, eps, device, precision, seed, keep_activations):
+        if not isinstance(model, PointNetSeg) or not isinstance(model_D, self._D_NET):
+            raise TypeError(f"{type(self).__name__}: expected a PointNetSeg and a "
+                            f"{self._D_NET.__name__}")
         if model_D.input_dim != model.output_dim:
             raise ValueError(f"model_D takes {model_D.input_dim} channels, the generator predicts "
                              f"{model.output_dim} classes")
         super().__init__(model, (optimizer, optimizer_D), [(lr, betas, eps), (lr_D, betas, eps)],
                          device, precision, keep_activations, model_D)
         self.lambda_seg, self.lambda_adv, self.seed = float(lambda_seg), float(lambda_adv), int(seed)
-        self.lambda_semi, self.semi_th = float(lambda_semi), float(semi_th)
-        # [loss_seg, loss_adv, loss_D, loss_D's GT part, its no-GT part, loss_semi]
+        # [loss_seg, loss_adv, loss_D, loss_D's GT part, its no-GT part, the subclass's term]
         self.loss_buf = torch.zeros(6, device=self.device)
-        self.kept_buf = torch.zeros(1, device=self.device, dtype=torch.int32)
-        self.d_out = self.semi_labels = None
+        self.d_out = None
         self._ws = None
-        self._semi_stale = False
 
     def __call__(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
                  apply_adam=True, semi=False):
-        from .discriminator import PWD_LOG_SOFTMAX, PWD_SOFTMAX, pwdisc_backward, pwdisc_forward, \
-            pwdisc_workspace
+        self._run(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, apply_adam, semi)
+        return self.losses
+
+    def _run(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, apply_adam,
+             semi=False):
+        """The step's launches and nothing else: what capture_on captures (reading
+        `losses` may launch, so it stays with __call__)."""
         B, N, _ = pts_gt.shape
         _check_dev(pts_gt, "pts_gt")
         _check_dev(pts_nogt, "pts_nogt", shape=(B, N, 3))
         if seg.shape != (B, N) or seg.dtype != torch.int64 or not seg.is_contiguous():
             raise ValueError("seg: expected contiguous int64 (B, N)")
-        if (B * N) % self.model_D.input_pts:
+        if self.model_D.fills_rows and (B * N) % self.model_D.input_pts:
             raise ValueError(f"{B} x {N} points do not fill rows of model_D.input_pts = "
                              f"{self.model_D.input_pts}")
         if semi and self.model_D.input_pts != N:
@@ -700,7 +699,8 @@ class SegAdvTrainStep(_SegStep):
             _engine().split(self.param, self.wph, self.wpl)
             wpl = self.wplanes
         pts = torch.cat([pts_gt, pts_nogt])
-        cls = torch.cat([cls_gt.float().reshape(B, 1, 16), cls_nogt.float().reshape(B, 1, 16)])
+        cls_gt = cls_gt.float().reshape(B, 1, 16)
+        cls = torch.cat([cls_gt, cls_nogt.float().reshape(B, 1, 16)])
         fw = seg_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
         ncls = fw["dims"][2]
         logits = fw["logits"]
@@ -710,16 +710,80 @@ class SegAdvTrainStep(_SegStep):
                                     _p(self.loss_buf), _p(d), _p(ws), ws.numel(), stream_ptr()),
               "pcadv_row_ce")
         if self._ws is None or self._ws[0] != M:
-            self._ws = (M, pwdisc_workspace(2 * M, self.device))
-        dws = self._ws[1]
+            self._ws = (M, self._d_workspace(2 * M, self.device))
+        d_out = self._disc(logits, ncls, M, N, cls_gt, d, self._ws[1],
+                           None if soft_gt is None else soft_gt.reshape(M),
+                           None if soft_nogt is None else soft_nogt.reshape(M), semi)
+        seg_backward(fw, d, None, out=self.grad_views)
+        if self.keep_activations:
+            self.fw, self.d_out = fw, d_out
+        if apply_adam:
+            self.adam()
+
+    def _disc(self, logits, ncls, M, N, cls_gt, d, dws, soft0, soft1, semi):
+        """D's fused forward and backward on logits' 2M rows: loss_buf[1:] and D's
+        gradients written, the no-GT rows of d filled.  Returns D's output."""
+        raise NotImplementedError
+
+    def adam(self):
+        """optimizer.step() and optimizer_D.step() (trainer.py:965-966, 1152-1153)."""
+        self._adam(0, self.lr, self.betas, self.eps)
+        self._adam(1, self.lr_D, self.betas_D, self.eps_D)
+
+    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
+                   semi=False):
+        """One HIP graph of a step reading the given resident buffers: a single
+        stream, no parallel branches (state is restored to what it was before
+        the warm-up).  `semi` is baked into the graph."""
+        def body():
+            self._run(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True, semi)
+        return self._capture(body, body)
+
+    def logged(self, with_semi=False):
+        """The last step's losses in the order of its loop's log line, as floats
+        (the loops' one host read per iteration).  The stacked step raises here
+        what BCELoss raises in the eager body."""
+        return (self.losses_semi if with_semi else self.losses).tolist()
+
+
+class SegAdvTrainStep(_SegDiscStep):
+    """One iteration of run_training_seg (utils/trainer.py:873-966) with
+    PointNetSeg + PointwiseDiscNet; the launches are _SegDiscStep's, with the
+    fused D forward on softmax(GT) / log_softmax(no-GT) (trainer.py:901,914)
+    giving loss_adv, loss_D and their derivatives.
+
+    The no-GT rows feed the adversarial term and D's own term from one forward
+    (D is frozen in the first and its input detached in the second, so the three
+    reference forwards compute the same values).
+
+    semi=True adds run_training_seg_semi's term (utils/trainer.py:1999-2024):
+    after the D backward, pcadv_row_semi_ce on the no-GT rows adds lambda_semi
+    times the cross entropy of the points whose D output is above semi_th
+    against their own argmax to those rows of dlogits (D receives nothing from
+    it).  It needs model_D.input_pts == N, as the reference's mask does.  The
+    term's loss and the number of kept points are `losses_semi[2]` and `kept`;
+    `losses` stays [loss_seg, loss_adv, loss_D].  A captured graph has `semi`
+    baked in: capture one graph per value."""
+
+    _D_NET, _d_workspace = PointwiseDiscNet, staticmethod(pwdisc_workspace)
+
+    def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
+                 lambda_adv=0.01, lr=1e-4, lr_D=1e-4, betas=(0.9, 0.999), eps=1e-8, device="cuda",
+                 precision=None, seed=0, keep_activations=False, lambda_semi=1.0, semi_th=0.8):
+        super().__init__(model, model_D, optimizer, optimizer_D, lambda_seg, lambda_adv, lr, lr_D,
+                         betas, eps, device, precision, seed, keep_activations)
+        self.lambda_semi, self.semi_th = float(lambda_semi), float(semi_th)
+        self.kept_buf = torch.zeros(1, device=self.device, dtype=torch.int32)  # loss_buf[5]: semi
+        self.semi_labels = None
+        self._semi_stale = False
+
+    def _disc(self, logits, ncls, M, N, cls_gt, d, dws, soft0, soft1, semi):
         out = torch.empty(2 * M, device=self.device)
         argc = torch.empty(2 * M, device=self.device, dtype=torch.int32)
         dout_d = torch.empty(2 * M, device=self.device)
         dout_adv = torch.empty(M, device=self.device)
         pwdisc_forward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, out, argc,
-                       dws, losses=self.loss_buf[1:5],
-                       soft0=None if soft_gt is None else soft_gt.reshape(M),
-                       soft1=None if soft_nogt is None else soft_nogt.reshape(M), seed=self.seed,
+                       dws, losses=self.loss_buf[1:5], soft0=soft0, soft1=soft1, seed=self.seed,
                        step_count=self.step_count, dout_d=dout_d, dout_adv=dout_adv)
         pwdisc_backward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, out, argc,
                         dws, dout_d, self.d_grad_views, dout_adv=dout_adv,
@@ -742,17 +806,9 @@ class SegAdvTrainStep(_SegStep):
             self.loss_buf[5:].zero_()
             self.kept_buf.zero_()
             self._semi_stale = False
-        seg_backward(fw, d, None, out=self.grad_views)
         if self.keep_activations:
-            self.fw, self.d_out, self.semi_labels = fw, out, labels
-        if apply_adam:
-            self.adam()
-        return self.losses
-
-    def adam(self):
-        """optimizer.step() and optimizer_D.step() (trainer.py:965-966)."""
-        self._adam(0, self.lr, self.betas, self.eps)
-        self._adam(1, self.lr_D, self.betas_D, self.eps_D)
+            self.semi_labels = labels
+        return out
 
     @property
     def losses(self):
@@ -771,30 +827,17 @@ class SegAdvTrainStep(_SegStep):
         int32; 0 for a step without the term)."""
         return self.kept_buf[0]
 
-    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
-                   semi=False):
-        """One HIP graph of a step reading the given resident buffers: a single
-        stream, no parallel branches (state is restored to what it was before
-        the warm-up).  `semi` is baked into the graph."""
-        def body():
-            self(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True, semi)
-        return self._capture(body, body)
 
-
-class SegStackTrainStep(_SegStep):
+class SegStackTrainStep(_SegDiscStep):
     """One iteration of run_training_seg_stack (utils/trainer.py:1053-1153) with
-    ImagePool(0), PointNetSeg + StackDiscNet and two Adams, as native launches
-    on one stream, capturable into a HIP graph:
+    PointNetSeg + StackDiscNet; the launches are _SegDiscStep's, where _disc is:
 
-      weight-plane split; seg_forward on the 2B clouds [GT; no-GT];
-      pcadv_row_ce on the GT rows (scale lambda_seg); the shape labels
-      (argmax of cls_gt, one per GT cloud) on the device; the fused stacked D
-      forward on softmax(GT) / log_softmax(no-GT) (trainer.py:1082,1095) with
-      loss_adv, loss_D, loss_D_shape, their derivatives with respect to the
-      per-point channel max, conv5's gradients and the bad_rows counter; the
-      fused D backward (conv1..conv4's gradients of loss_D + lambda_disc_shape
-      loss_D_shape, and the no-GT rows of dlogits from lambda_adv loss_adv
-      through the frozen D); seg_backward; the two Adam updates.
+      the shape labels (argmax of cls_gt, one per GT cloud) on the device; the
+      fused stacked D forward on softmax(GT) / log_softmax(no-GT)
+      (trainer.py:1082,1095) with loss_adv, loss_D, loss_D_shape, their
+      derivatives with respect to the per-point channel max, conv5's gradients
+      and the bad_rows counter; the fused D backward (conv1..conv4's gradients
+      of loss_D + lambda_disc_shape loss_D_shape, and the no-GT rows of dlogits).
 
     One D forward serves each half.  With ImagePool(0) the reference's two
     forwards of D on the GT predictions (trainer.py:1117 for the shape term,
@@ -808,66 +851,29 @@ class SegStackTrainStep(_SegStep):
     line; loss_D_shape unscaled).  `bad_rows` (device int32) counts the points
     whose D output left [0, 1] in the last step: torch's BCELoss raises there,
     a captured graph cannot, so the caller checks the counter when it reads the
-    losses.  Soft labels: explicit (soft_gt / soft_nogt, one per point) or
-    drawn on the device keyed by (seed, the generator's step counter, row), the
-    draws of SegAdvTrainStep for the same seed.  D always runs in f32."""
+    losses (`logged` does)."""
+
+    _D_NET, _d_workspace = StackDiscNet, staticmethod(stackdisc_workspace)
 
     def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
                  lambda_adv=0.01, lambda_disc_shape=1.0, lr=1e-4, lr_D=1e-4, betas=(0.9, 0.999),
                  eps=1e-8, device="cuda", precision=None, seed=0, keep_activations=False):
-        from .discriminator import StackDiscNet
-        if not isinstance(model, PointNetSeg) or not isinstance(model_D, StackDiscNet):
-            raise TypeError("SegStackTrainStep: expected a PointNetSeg and a StackDiscNet")
-        if model_D.input_dim != model.output_dim:
-            raise ValueError(f"model_D takes {model_D.input_dim} channels, the generator predicts "
-                             f"{model.output_dim} classes")
-        if model_D.num_shapes < 16:
+        if isinstance(model_D, StackDiscNet) and model_D.num_shapes < 16:
             raise ValueError(f"model_D has {model_D.num_shapes} shape classes, cls is 16 wide")
-        super().__init__(model, (optimizer, optimizer_D), [(lr, betas, eps), (lr_D, betas, eps)],
-                         device, precision, keep_activations, model_D)
-        self.lambda_seg, self.lambda_adv = float(lambda_seg), float(lambda_adv)
-        self.lambda_disc_shape, self.seed = float(lambda_disc_shape), int(seed)
-        # [loss_seg, loss_adv, loss_D, loss_D's GT part, its no-GT part, loss_D_shape]
-        self.loss_buf = torch.zeros(6, device=self.device)
-        self.bad_buf = torch.zeros(1, device=self.device, dtype=torch.int32)
+        super().__init__(model, model_D, optimizer, optimizer_D, lambda_seg, lambda_adv, lr, lr_D,
+                         betas, eps, device, precision, seed, keep_activations)
+        self.lambda_disc_shape = float(lambda_disc_shape)
+        self.bad_buf = torch.zeros(1, device=self.device, dtype=torch.int32)  # loss_buf[5]: shape
         self._loss_idx = torch.tensor([0, 1, 2, 5], device=self.device)  # the log line's order
-        self.d_out = None
-        self._ws = None
 
     def __call__(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
                  apply_adam=True):
-        self._run(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, apply_adam)
-        return self.losses
+        return super().__call__(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt,
+                                apply_adam)
 
-    def _run(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, apply_adam):
-        from .discriminator import PWD_LOG_SOFTMAX, PWD_SOFTMAX, stackdisc_backward, \
-            stackdisc_forward, stackdisc_workspace
-        B, N, _ = pts_gt.shape
-        _check_dev(pts_gt, "pts_gt")
-        _check_dev(pts_nogt, "pts_nogt", shape=(B, N, 3))
-        if seg.shape != (B, N) or seg.dtype != torch.int64 or not seg.is_contiguous():
-            raise ValueError("seg: expected contiguous int64 (B, N)")
-        M = B * N
-        wpl = None
-        if _PLANES:  # every weight's planes (fp32 mode reads conv6's only)
-            _engine().split(self.param, self.wph, self.wpl)
-            wpl = self.wplanes
-        pts = torch.cat([pts_gt, pts_nogt])
-        cls_gt = cls_gt.float().reshape(B, 1, 16)
-        cls = torch.cat([cls_gt, cls_nogt.float().reshape(B, 1, 16)])
-        fw = seg_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
-        ncls = fw["dims"][2]
-        logits = fw["logits"]
-        d = torch.empty(2 * M, ncls, device=self.device)
-        ws = _ws(self.lib.pcadv_row_ce_workspace_bytes(M), self.device)
-        check(self.lib.pcadv_row_ce(_p(logits), ncls, _p(seg), M, ncls, self.lambda_seg,
-                                    _p(self.loss_buf), _p(d), _p(ws), ws.numel(), stream_ptr()),
-              "pcadv_row_ce")
-        if self._ws is None or self._ws[0] != M:
-            self._ws = (M, stackdisc_workspace(2 * M, self.device))
-        dws = self._ws[1]
+    def _disc(self, logits, ncls, M, N, cls_gt, d, dws, soft0, soft1, semi):
         # make_shape_label (utils/utils.py:33-38): one label per GT cloud
-        shape_label = torch.argmax(cls_gt.reshape(B, 16), dim=1).to(torch.int32)
+        shape_label = torch.argmax(cls_gt.reshape(M // N, 16), dim=1).to(torch.int32)
         m = torch.empty(2 * M, device=self.device)
         d_out = torch.empty(2 * M, device=self.device)
         argc = torch.empty(2 * M, device=self.device, dtype=torch.int32)
@@ -875,24 +881,13 @@ class SegStackTrainStep(_SegStep):
         dm_adv = torch.empty(M, device=self.device)
         stackdisc_forward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, m, argc,
                           d_out, dws, losses=self.loss_buf[1:6], shape_label=shape_label,
-                          pts_per_cloud=N, lambda_disc_shape=self.lambda_disc_shape,
-                          soft0=None if soft_gt is None else soft_gt.reshape(M),
-                          soft1=None if soft_nogt is None else soft_nogt.reshape(M),
-                          seed=self.seed, step_count=self.step_count, dm_d=dm_d, dm_adv=dm_adv,
-                          grads5=self.d_grad_views[8:10], bad_rows=self.bad_buf)
+                          pts_per_cloud=N, lambda_disc_shape=self.lambda_disc_shape, soft0=soft0,
+                          soft1=soft1, seed=self.seed, step_count=self.step_count, dm_d=dm_d,
+                          dm_adv=dm_adv, grads5=self.d_grad_views[8:10], bad_rows=self.bad_buf)
         stackdisc_backward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, m,
                            argc, dws, dm_d, self.d_grad_views, dm_adv=dm_adv,
                            lambda_adv=self.lambda_adv, dlogits=d)
-        seg_backward(fw, d, None, out=self.grad_views)
-        if self.keep_activations:
-            self.fw, self.d_out = fw, d_out
-        if apply_adam:
-            self.adam()
-
-    def adam(self):
-        """optimizer.step() and optimizer_D.step() (trainer.py:1152-1153)."""
-        self._adam(0, self.lr, self.betas, self.eps)
-        self._adam(1, self.lr_D, self.betas_D, self.eps_D)
+        return d_out
 
     @property
     def losses(self):
@@ -908,9 +903,12 @@ class SegStackTrainStep(_SegStep):
         return self.bad_buf[0]
 
     def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None):
-        """One HIP graph of a step reading the given resident buffers: a single
-        stream, no parallel branches (state is restored to what it was before
-        the warm-up)."""
-        def body():
-            self._run(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True)
-        return self._capture(body, body)
+        """_SegDiscStep.capture_on (this step has no semi term).  Reading `losses`
+        launches its gather, so that stays outside the graph."""
+        return super().capture_on(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt)
+
+    def logged(self, with_semi=False):
+        vals = self.losses.tolist()
+        if int(self.bad_rows.item()) > 0:
+            raise RuntimeError("all elements of input should be between 0 and 1")
+        return vals

@@ -1206,11 +1206,17 @@ def _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
 
 
 def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, pool_gt, pool_nogt,
-                  pts, cls, seg, pts_nogt, cls_nogt, args, semi_loss=None, semi=False):
+                  pts, cls, seg, pts_nogt, cls_nogt, args, semi_loss=None, semi=False,
+                  shape_criterion=None):
     """utils/trainer.py:881-966 through autograd over the same modules: returns
     [loss_seg, loss_adv, loss_D].  With a semi_loss, :1956-2061: `semi` is the
     iteration's (args.semi_start > 0 and i_iter > args.semi_start) and the
-    values are [loss_seg, loss_adv, loss_semi, loss_D]."""
+    values are [loss_seg, loss_adv, loss_semi, loss_D].  With a shape_criterion,
+    :1059-1153 (model_D returns (shape logits, D_out); gan_loss is applied to
+    D's probability output, so torch's own BCELoss range checks apply): the
+    values are [loss_seg, loss_adv, loss_D, loss_D_shape]."""
+    stack = shape_criterion is not None
+    disc = (lambda x: model_D(x)[1]) if stack else model_D
     optimizer.zero_grad()
     optimizer_D.zero_grad()
     for param in model_D.parameters():  # train G
@@ -1220,7 +1226,7 @@ def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, po
     pred_gt_softmax = F.softmax(pred, dim=1)
     pred_nogt, _ = model(pts_nogt, cls_nogt)
     pred_nogt_softmax = F.log_softmax(pred_nogt, dim=1)
-    D_out = model_D(pred_nogt_softmax)
+    D_out = disc(pred_nogt_softmax)
     loss_adv = gan_loss(D_out, make_D_label(input=D_out, value=1, device=args.device, random=False))
     loss = args.lambda_seg * l_seg + args.lambda_adv * loss_adv
     loss_semi_value = 0.0
@@ -1235,54 +1241,26 @@ def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, po
     loss.backward()
     for param in model_D.parameters():  # train D
         param.requires_grad = True
+    pred_gt_softmax = pred_gt_softmax.detach()
+    if stack:  # the shape term's backward comes before the two pooled terms', as the reference's
+        S_out_gt, _ = model_D(pred_gt_softmax)
+        shape = make_shape_label(input=cls.squeeze(1), npts=S_out_gt.shape[2])
+        loss_D_shape = shape_criterion(S_out_gt, shape)
+        (args.lambda_disc_shape * loss_D_shape).backward()
     loss_D_value = 0.0
     for pool, x, value in ((pool_gt, pred_gt_softmax, 1), (pool_nogt, pred_nogt_softmax, 0)):
-        D_out = model_D(pool.query(x.detach()))
+        D_out = disc(pool.query(x.detach()))
         loss_D = 0.5 * gan_loss(D_out, make_D_label(input=D_out, value=value, device=args.device,
                                                     random=True))
         loss_D.backward()
         loss_D_value += loss_D.item()
     optimizer.step()  # the reference steps G before D's part: D is frozen there, the same values
     optimizer_D.step()
+    if stack:
+        return [l_seg.item(), loss_adv.item(), loss_D_value, loss_D_shape.item()]
     if semi_loss is None:
         return [l_seg.item(), loss_adv.item(), loss_D_value]
     return [l_seg.item(), loss_adv.item(), loss_semi_value, loss_D_value]
-
-
-def _seg_stack_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, shape_criterion,
-                    pool_gt, pool_nogt, pts, cls, seg, pts_nogt, cls_nogt, args):
-    """utils/trainer.py:1059-1153 through autograd over the same modules: returns
-    [loss_seg, loss_adv, loss_D, loss_D_shape].  gan_loss is applied to D's
-    probability output, so torch's own BCELoss range checks apply here."""
-    optimizer.zero_grad()
-    optimizer_D.zero_grad()
-    for param in model_D.parameters():  # train G
-        param.requires_grad = False
-    pred, _ = model(pts, cls)
-    l_seg = seg_loss(pred, seg)
-    pred_gt_softmax = F.softmax(pred, dim=1)
-    pred_nogt, _ = model(pts_nogt, cls_nogt)
-    pred_nogt_softmax = F.log_softmax(pred_nogt, dim=1)
-    _, D_out = model_D(pred_nogt_softmax)
-    loss_adv = gan_loss(D_out, make_D_label(input=D_out, value=1, device=args.device, random=False))
-    (args.lambda_seg * l_seg + args.lambda_adv * loss_adv).backward()
-    for param in model_D.parameters():  # train D
-        param.requires_grad = True
-    pred_gt_softmax = pred_gt_softmax.detach()
-    S_out_gt, _ = model_D(pred_gt_softmax)
-    shape = make_shape_label(input=cls.squeeze(1), npts=S_out_gt.shape[2])
-    loss_D_shape = shape_criterion(S_out_gt, shape)
-    (args.lambda_disc_shape * loss_D_shape).backward()
-    loss_D_value = 0.0
-    for pool, x, value in ((pool_gt, pred_gt_softmax, 1), (pool_nogt, pred_nogt_softmax, 0)):
-        _, D_out = model_D(pool.query(x.detach()))
-        loss_D = 0.5 * gan_loss(D_out, make_D_label(input=D_out, value=value, device=args.device,
-                                                    random=True))
-        loss_D.backward()
-        loss_D_value += loss_D.item()
-    optimizer.step()
-    optimizer_D.step()
-    return [l_seg.item(), loss_adv.item(), loss_D_value, loss_D_shape.item()]
 
 
 def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetloader_nogt_iter,
@@ -1304,10 +1282,11 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
     shape_criterion, BCELoss (mean, no weight) and ImagePool(0): every
     iteration with equal batch shapes is one SegStackTrainStep (any point
     count: this D does not use input_pts), after which bad_rows > 0 raises
-    BCELoss's error; everything else runs _seg_stack_body (see
-    run_training_seg_stack).  Where the reference loops differ, so do these:
-    the fused step's condition, the log line, the tensorboard tags, and the
-    checkpoint by accuracy that the semi loop does not write."""
+    BCELoss's error (step.logged); everything else runs _seg_adv_body with the
+    shape_criterion (see run_training_seg_stack).  Where the reference loops
+    differ, so do these: the fused step's class and condition, the log line,
+    the tensorboard tags, and the checkpoint by accuracy that the semi loop does
+    not write; all of it is chosen here, before the loop."""
     from .seg import SegAdvTrainStep, SegStackTrainStep
     with_semi, stack = semi_loss is not None, shape_criterion is not None
     max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
@@ -1315,18 +1294,20 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
     fusable = _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
                                history_pool_gt, history_pool_nogt, args, shape_criterion) \
         and (not with_semi or _semi_fusable(semi_loss))
-    semi_args = dict(lambda_semi=float(getattr(args, "lambda_semi", 1.0)),
-                     semi_th=float(getattr(args, "semi_TH", 0.8))) if with_semi else {}
     step, eager_since = None, False
     tb = getattr(args, "tensorboard", False) and writer is not None
-    if with_semi:
-        line = ('iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} loss semi = {4:.3f} '
-                'loss_D = {5:.3f}')
-    elif stack:
-        line = ('iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} loss_D = {4:.3f} '
-                'loss_D_shape = {5:.3f} ')
+    line = 'iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} '
+    if stack:
+        Step, step_args = SegStackTrainStep, dict(lambda_disc_shape=args.lambda_disc_shape)
+        line += 'loss_D = {4:.3f} loss_D_shape = {5:.3f} '
+        d_tags = (('Loss/train_D', 2), ('Loss/train_D_shape', 3))
     else:
-        line = 'iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} loss_D = {4:.3f} '
+        Step, step_args = SegAdvTrainStep, {}
+        line += 'loss semi = {4:.3f} loss_D = {5:.3f}' if with_semi else 'loss_D = {4:.3f} '
+        d_tags = (('Loss/train_disc', -1),)
+        if with_semi:
+            step_args = dict(lambda_semi=float(getattr(args, "lambda_semi", 1.0)),
+                             semi_th=float(getattr(args, "semi_TH", 0.8)))
 
     def save(tag):
         if step is not None:
@@ -1345,58 +1326,37 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
         pts_nogt, cls_nogt = batch
         pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
         semi = with_semi and args.semi_start > 0 and i_iter > args.semi_start
-        # D's rows are input_pts points each: any whole number of them, but the
-        # semi loop's mask indexes (B, N), as the reference's does
+        # PointwiseDiscNet's rows are input_pts points each: any whole number of
+        # them, but the semi loop's mask indexes (B, N), as the reference's does
         if fusable and pts.shape == pts_nogt.shape and (
                 model_D.input_pts == pts.shape[1] if with_semi
                 else stack or (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0):
-            if step is None and stack:
-                step = SegStackTrainStep(model, model_D, optimizer=optimizer,
-                                         optimizer_D=optimizer_D, lambda_seg=args.lambda_seg,
-                                         lambda_adv=args.lambda_adv,
-                                         lambda_disc_shape=args.lambda_disc_shape,
-                                         device=args.device,
-                                         seed=int(getattr(args, "seed", 0) or 0))
-            elif step is None:
-                step = SegAdvTrainStep(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
-                                       lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
-                                       device=args.device, seed=int(getattr(args, "seed", 0) or 0),
-                                       **semi_args)
+            if step is None:
+                step = Step(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
+                            lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
+                            device=args.device, seed=int(getattr(args, "seed", 0) or 0),
+                            **step_args)
             elif eager_since:
                 step.after_eager()
             eager_since = False
             step.sync_hyper()
-            if stack:
-                step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
-                     cls_nogt.contiguous())
-                vals = step.losses.tolist()
-                if int(step.bad_rows.item()) > 0:  # what BCELoss raises in the eager body
-                    raise RuntimeError("all elements of input should be between 0 and 1")
-            else:
-                step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
-                     cls_nogt.contiguous(), semi=semi)
-                vals = (step.losses_semi if with_semi else step.losses).tolist()
+            step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
+                 cls_nogt.contiguous(), **({"semi": True} if semi else {}))
+            vals = step.logged(with_semi)
         else:
             if step is not None:
                 step.sync_optimizer_state()
             eager_since = True
-            if stack:
-                vals = _seg_stack_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                                       shape_criterion, history_pool_gt, history_pool_nogt, pts,
-                                       cls, seg, pts_nogt, cls_nogt, args)
-            else:
-                vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                                     history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
-                                     cls_nogt, args, semi_loss=semi_loss, semi=semi)
+            vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                                 history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
+                                 cls_nogt, args, semi_loss=semi_loss, semi=semi,
+                                 shape_criterion=shape_criterion)
         train_logger.info(line.format(i_iter, args.total_iterations, *vals))
         if tb:
             writer.add_scalar('Loss/train_seg', vals[0], i_iter)
             writer.add_scalar('Loss/train_adv', vals[1], i_iter)
-            if stack:
-                writer.add_scalar('Loss/train_D', vals[2], i_iter)
-                writer.add_scalar('Loss/train_D_shape', vals[3], i_iter)
-            else:
-                writer.add_scalar('Loss/train_disc', vals[-1], i_iter)
+            for tag, k in d_tags:
+                writer.add_scalar(tag, vals[k], i_iter)
         if i_iter % args.iter_test_epoch == 0:
             ep = i_iter // args.iter_test_epoch
             save("epoch_{}".format(ep))
@@ -1471,7 +1431,7 @@ def run_training_seg_stack(trainloader_gt, trainloader_nogt, trainloader_gt_iter
     for seg_loss and shape_criterion, BCELoss (mean, no weight), both pools of
     size 0 and the HIP device, every iteration whose two batches have the same
     shape is one SegStackTrainStep; anything else runs the reference's body
-    through autograd over the same modules (_seg_stack_body), where torch's own
+    through autograd over the same modules (_seg_adv_body), where torch's own
     BCELoss checks apply.
 
     A D output outside [0, 1] (a trained conv5 bias can push the logsumexp

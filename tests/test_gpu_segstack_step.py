@@ -181,9 +181,9 @@ def test_step_vs_autograd_body(B, N, monkeypatch):
     _replay_labels(monkeypatch, soft)
     args = argparse.Namespace(device=DEV, lambda_seg=lam_seg, lambda_adv=lam_adv,
                               lambda_disc_shape=lam_shape)
-    want = trainer._seg_stack_body(m2, d2, mk(m2), mk(d2), _SoftBCE(), torch.nn.CrossEntropyLoss(),
-                                   torch.nn.CrossEntropyLoss(), ImagePool(0), ImagePool(0), pts,
-                                   cls, seg, pts_ng, cls_ng, args)
+    want = trainer._seg_adv_body(m2, d2, mk(m2), mk(d2), _SoftBCE(), torch.nn.CrossEntropyLoss(),
+                                 ImagePool(0), ImagePool(0), pts, cls, seg, pts_ng, cls_ng, args,
+                                 shape_criterion=torch.nn.CrossEntropyLoss())
     print("fused", losses, "autograd", want)
     assert np.max(np.abs(np.array(losses) - np.array(want))) <= 1e-5
     names = [f"{w}.{n}" for w, mod in (("G", m), ("D", d)) for n, _ in mod.named_parameters()]
