@@ -10,7 +10,9 @@ its native training step SegTrainStep; PointwiseDiscNet
 (models/discriminator.py:53-79) and the adversarial segmentation step
 SegAdvTrainStep (run_training_seg, and run_training_seg_semi with its
 pseudo-label term); StackDiscNet (models/discriminator.py:139-175) and
-SegStackTrainStep (run_training_seg_stack); run_training_semi; the HDF5 datasets of
+SegStackTrainStep (run_training_seg_stack); PointNetSeg_regulization
+(models/pointnet.py:205-259) and SegStackReguTrainStep
+(run_training_seg_stack_regulization); run_training_semi; the HDF5 datasets of
 dataset/modelNetData.py and dataset/shapeNetData.py without h5py, with a
 device-resident batch loader (dataset.DeviceCloudLoader) and native test
 passes over it (evaluate.ClsEvaluator / SegEvaluator).  All compute runs in
@@ -21,11 +23,13 @@ from ._lib import use_stream_graph_dispatch  # noqa: E402
 from .discriminator import DeepConvDiscNet, PointwiseDiscNet, StackDiscNet  # noqa: E402
 from .evaluate import ClsEvaluator, SegEvaluator  # noqa: E402
 from .pointnet import PointNetCls, PointNetfeat, STN3d, STNkd, feature_transform_regularizer  # noqa: E402,E501
-from .seg import PointNetSeg, SegAdvTrainStep, SegStackTrainStep, SegTrainStep  # noqa: E402
+from .seg import (PointNetSeg, PointNetSeg_regulization, SegAdvTrainStep,  # noqa: E402
+                  SegStackReguTrainStep, SegStackTrainStep, SegTrainStep)
 from .step import AdvTrainStep  # noqa: E402
 
 __all__ = ["PointNetCls", "PointNetfeat", "STN3d", "STNkd", "DeepConvDiscNet",
            "feature_transform_regularizer", "AdvTrainStep", "PointNetSeg", "SegTrainStep",
            "PointwiseDiscNet", "SegAdvTrainStep", "StackDiscNet", "SegStackTrainStep",
+           "PointNetSeg_regulization", "SegStackReguTrainStep",
            "ClsEvaluator", "SegEvaluator"]
 __version__ = "0.1.0"

@@ -239,6 +239,10 @@ SIGNATURES = {
     "pcadv_stackdisc_workspace_bytes": (_sz, [_i64, _i]),
     "pcadv_stackdisc_forward": (_i, [ctypes.POINTER(StackdiscArgs), _vp]),
     "pcadv_stackdisc_backward": (_i, [ctypes.POINTER(StackdiscArgs), _vp]),
+    "pcadv_cloud_xform_fwd": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "pcadv_cloud_xform_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i, _i, _i,
+                                   _i, _vp]),
+    "pcadv_tnet_mse_reg": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -55,9 +55,9 @@ def init_weights(net, init_type, init_gain=1.0, verbose=True):
 
 def load_models(mode, device, args):
     """utils/model_utils.py:60-140 for the hot path's modes 'cls' and 'disc', the
-    segmentation row's 'seg', its per-point discriminator 'disc_seg' and the
-    stacked shape discriminator 'disc_stack'.  The dual discriminator and the
-    regularised generator are outside this build's scope."""
+    segmentation row's 'seg', its per-point discriminator 'disc_seg', the
+    stacked shape discriminator 'disc_stack' and the regularised generator
+    'seg_regu'.  The dual discriminator is outside this build's scope."""
     if mode == "cls":
         model = PointNetCls(k=40, feature_transform=False).to(device)
         try:
@@ -87,7 +87,15 @@ def load_models(mode, device, args):
     elif mode == "disc_stack":  # StackDiscNet (run_training_seg_stack's D)
         model = StackDiscNet(input_pts=args.input_pts, input_dim=args.disc_indim, num_shapes=16)
         model = init_net(model, device, init_type=args.init_disc)
-    elif mode in ("seg_regu", "disc_dual"):
+    elif mode == "seg_regu":  # :92-103, PointNetSeg_regulization, initialised like a discriminator
+        from .seg import PointNetSeg_regulization
+        model = PointNetSeg_regulization(NUM_SEG_CLASSES=50)
+        model = init_net(model, device, init_type=args.init_disc)
+        if getattr(args, "checkpoint", None):
+            print("Loading pretrained cls model ...")
+            model.load_state_dict(torch.load(args.checkpoint, map_location=device,
+                                             weights_only=True))
+    elif mode == "disc_dual":
         raise NotImplementedError(f"mode {mode!r} is outside the adversarial cls hot path")
     else:
         raise ValueError("Invalid mode {}!".format(mode))

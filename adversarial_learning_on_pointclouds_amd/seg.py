@@ -35,16 +35,18 @@ import ctypes
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, ops
 from ._lib import check, stream_ptr
 from .discriminator import (PWD_LOG_SOFTMAX, PWD_SOFTMAX, PointwiseDiscNet, StackDiscNet,
                             pwdisc_backward, pwdisc_forward, pwdisc_workspace, stackdisc_backward,
                             stackdisc_forward, stackdisc_workspace)
 from .flat import FlatAdam
+from .pointnet import STN3d, STNkd
 from .step import FusedStep
 
-__all__ = ["PointNetSeg", "SegTrainStep", "SegAdvTrainStep", "SegStackTrainStep",
-           "seg_cross_entropy", "seg_forward", "seg_backward"]
+__all__ = ["PointNetSeg", "PointNetSeg_regulization", "SegTrainStep", "SegAdvTrainStep",
+           "SegStackTrainStep", "SegStackReguTrainStep", "seg_cross_entropy", "seg_forward",
+           "seg_backward", "segregu_forward", "segregu_backward"]
 
 _LOC = 960                       # x1..x5 widths 64 + 128 + 128 + 128 + 512
 PRECISIONS = ("fp32", "bf16x3")
@@ -177,6 +179,34 @@ class _Engine:
             self.wgrad(*wargs, fin=fin, **wkw)
             self.gemm_run(g)
 
+    def xform_fwd(self, x, ldx, T, y, ldy, C, Npts, k, *, x_off=0):
+        """y = x T per cloud (pcadv_cloud_xform_fwd)."""
+        check(self.lib.pcadv_cloud_xform_fwd(_p(x, x_off), ldx, _p(T), _p(y), ldy, C, Npts, k,
+                                             stream_ptr()), "pcadv_cloud_xform_fwd")
+
+    def xform_bwd(self, dy, lddy, x, ldx, T, C, Npts, k, *, dT=None, accumulate=False, dx=None,
+                  lddx=0, add=None, relu_x=False, x_off=0, dx_off=0):
+        """dT (+)= x^T dy and / or dx += (dy T^T + add) [x > 0] (pcadv_cloud_xform_bwd)."""
+        check(self.lib.pcadv_cloud_xform_bwd(
+            _p(dy), lddy, _p(x, x_off), ldx, _p(T), None if dT is None else _p(dT),
+            int(accumulate), None if dx is None else _p(dx, dx_off), lddx,
+            None if add is None else _p(add), int(relu_x), C, Npts, k, stream_ptr()),
+            "pcadv_cloud_xform_bwd")
+
+    def mse_reg(self, T, B0, scale, loss, dT=None, ws=None):
+        """loss[0:2] = MSELoss(T T^T, I) of the first B0 clouds and of the rest;
+        dT += scale x its gradient (pcadv_tnet_mse_reg).  ws: the call's
+        workspace, at least 4 C f32 (the row-block sums of the C clouds, include/
+        pcadv.h); a step passes its resident one, else it is allocated here."""
+        C, k, _ = T.shape
+        if ws is None:
+            ws = torch.empty(4 * max(C, 1), device=T.device)
+        elif ws.dtype != torch.float32 or ws.numel() < 4 * C:
+            raise ValueError(f"mse_reg: workspace of {ws.numel()} elements, needs {4 * C} f32")
+        check(self.lib.pcadv_tnet_mse_reg(_p(T), C, B0, k, float(scale), _p(loss),
+                                          None if dT is None else _p(dT), _p(ws), stream_ptr()),
+              "pcadv_tnet_mse_reg")
+
     def colsum(self, x, ld, M, N, out, *, ymask=None, ldm=0, x_off=0, m_off=0):
         nb = self.lib.pcadv_colsum_workspace_bytes(M, N)
         ws = _ws(nb, x.device)
@@ -243,6 +273,61 @@ def seg_forward(pts, cls, params, wplanes=None, precision="fp32"):
     activation the backward needs.  Each layer's epilogue also writes its
     output's bf16 hi / lo planes, which the next layer's GEMM stages as they
     are (no per-tile splitting)."""
+    return _forward(pts, cls, params, wplanes, precision)
+
+
+def segregu_forward(pts, cls, params, wplanes=None, precision="fp32"):
+    """PointNetSeg_regulization forward (pointnet.py:226-259) on the engine:
+    seg_forward with the two T-Nets spliced in.  params: the 44 parameters in
+    state_dict order (stn, fstn, conv1..conv6, fc1..fc4); wplanes likewise.
+    The dict also holds T3 (B, 3, 3), trans_feat (B, 128, 128), the
+    transformed points and x3 (conv1's and conv4's inputs) and the T-Nets'
+    activations.  The T-Nets run on their f32 kernels in both precisions."""
+    return _forward(pts, cls, params[_NTN:], None if wplanes is None else wplanes[_NTN:],
+                    precision, tn=params[:_NTN])
+
+
+_NTN = 24  # parameters of stn + fstn, ahead of conv1 in PointNetSeg_regulization's state_dict
+
+
+def _tnet_forward(x, p, k):
+    """STN3d / STNkd (pointnet.py:26-43,59-79) on point-major x (B, N, k) through
+    the native point-wise, conv + max and linear ops: T (B, k, k) and the
+    activations its backward reads."""
+    h1 = ops.pw_fwd(x, p[0], p[1], ops.ACT_RELU)
+    h2 = ops.pw_fwd(h1, p[2], p[3], ops.ACT_RELU)
+    g, gidx = ops.conv_max_fwd(h2, p[4], p[5], True)
+    f1 = ops.linear_fwd(g, p[6], p[7], ops.ACT_RELU)
+    f2 = ops.linear_fwd(f1, p[8], p[9], ops.ACT_RELU)
+    t = ops.linear_fwd(f2, p[10], p[11], ops.ACT_NONE, add_identity_k=k)
+    return t.view(-1, k, k), dict(x=x, h1=h1, h2=h2, g=g, gidx=gidx, f1=f1, f2=f2, t=t, p=list(p))
+
+
+def _tnet_backward(c, dT, out, need_dx):
+    """Gradients of a T-Net's 12 parameters, written into out[0:12], given dL/dT;
+    returns dL/dx (B, N, k) when asked."""
+    p, k = c["p"], c["x"].shape[2]
+    dt = dT.reshape(dT.shape[0], -1)
+    df2, _, _ = ops.linear_bwd(dt, c["t"], ops.ACT_NONE, None, 0.0, c["f2"], p[10],
+                               dw_out=out[10], db_out=out[11])
+    df1, _, _ = ops.linear_bwd(df2, c["f2"], ops.ACT_RELU, None, 0.0, c["f1"], p[8],
+                               dw_out=out[8], db_out=out[9])
+    dg, _, _ = ops.linear_bwd(df1, c["f1"], ops.ACT_RELU, None, 0.0, c["g"], p[6],
+                              dw_out=out[6], db_out=out[7])
+    # the ReLU before the max and conv2's own: dz2 comes back masked
+    dz2, _, _ = ops.conv_max_bwd(dg, c["gidx"], c["h2"], p[4], gmax_relu=c["g"], dw_out=out[4],
+                                 db_out=out[5], dx_relu=True)
+    ops.pw_bwd_weight(dz2, None, ops.ACT_NONE, c["h1"], dw_out=out[2], db_out=out[3])
+    dh1 = ops.pw_bwd_data(dz2, None, ops.ACT_NONE, _wmat(p[2]), 64)
+    ops.pw_bwd_weight(dh1, c["h1"], ops.ACT_RELU, c["x"], dw_out=out[0], db_out=out[1])
+    if need_dx:
+        return ops.pw_bwd_data(dh1, c["h1"], ops.ACT_RELU, _wmat(p[0]), k)
+    return None
+
+
+def _forward(pts, cls, params, wplanes, precision, tn=None):
+    """seg_forward, or with tn (the 24 T-Net parameters) segregu_forward: the
+    conv / fc / conv6-max / fc1-split code both share."""
     E = _engine()
     B, N, _ = pts.shape
     M = B * N
@@ -270,18 +355,37 @@ def seg_forward(pts, cls, params, wplanes=None, precision="fp32"):
         x5p, x5ld, x5off = xp, _LOC, _OFF[4]
     elif c6p:
         x5p, x5ld, x5off = pl(M, 512), 512, 0
+    # the input transform (pointnet.py:229-231): conv1 reads p' = pts T3
+    pin, tnet = pts, None
+    if tn is not None:
+        T3, c3 = _tnet_forward(pts, tn[:12], 3)
+        pin = torch.empty(M, 3, device=dev)
+        E.xform_fwd(pts, 3, T3, pin, 3, B, N, 3)
     # conv1..conv5 + ReLU into the column blocks of xloc
-    E.gemm(pts, 3, W[0], 3, xloc, _LOC, M, 64, 3, bias=bc[0], relu=True, c_off=_OFF[0],
+    E.gemm(pin, 3, W[0], 3, xloc, _LOC, M, 64, 3, bias=bc[0], relu=True, c_off=_OFF[0],
            precise=pf, cp=xp if planes else None, ldcp=_LOC, cp_off=_OFF[0])
     for i in range(1, 5):
         K, O = _CONV[i]
+        a, lda, a_off, ap = xloc, _LOC, _OFF[i - 1], xp if planes else None
+        if i == 3 and tn is not None:
+            # the feature transform (pointnet.py:237-239): fstn on a dense copy of x3,
+            # conv4 reads x3t = x3 T from its own buffer; xloc keeps x3 for fc1
+            x3d = xloc[:, _OFF[2]:_OFF[3]].contiguous().view(B, N, 128)
+            T, cf = _tnet_forward(x3d, tn[12:], 128)
+            x3t = torch.empty(M, 128, device=dev)
+            E.xform_fwd(xloc, _LOC, T, x3t, 128, B, N, 128, x_off=_OFF[2])
+            tnet = dict(T3=T3, T=T, c3=c3, cf=cf, pin=pin, x3t=x3t)
+            a, lda, a_off = x3t, 128, 0
+            if planes:
+                ap = pl(M, 128)
+                E.split(x3t, *ap)
         if planes:
-            E.gemm_bf2(xp, _LOC, Wp[i], K, xloc, _LOC, M, O, K, bias=bc[i], relu=True,
-                       a_off=_OFF[i - 1], c_off=_OFF[i], cp=xp, ldcp=_LOC, cp_off=_OFF[i])
+            E.gemm_bf2(ap, lda, Wp[i], K, xloc, _LOC, M, O, K, bias=bc[i], relu=True,
+                       a_off=a_off, c_off=_OFF[i], cp=xp, ldcp=_LOC, cp_off=_OFF[i])
         else:
             last = i == 4 and c6p  # conv5 also writes x5's planes for conv6's screen
-            E.gemm(xloc, _LOC, W[i], K, xloc, _LOC, M, O, K, bias=bc[i], relu=True,
-                   a_off=_OFF[i - 1], c_off=_OFF[i], precise=pf, cp=x5p if last else None,
+            E.gemm(a, lda, W[i], K, xloc, _LOC, M, O, K, bias=bc[i], relu=True,
+                   a_off=a_off, c_off=_OFF[i], precise=pf, cp=x5p if last else None,
                    ldcp=x5ld if last else 0)
     # conv6 + ReLU + max over the points of each cloud
     gmax = torch.empty(B, 2048, device=dev)
@@ -329,14 +433,39 @@ def seg_forward(pts, cls, params, wplanes=None, precision="fp32"):
     return dict(pts=pts, cvec=cvec, xloc=xloc, gmax=gmax, gidx=gidx, h1=h1, h2=h2, h3=h3, W=W,
                 Wf=Wf, logits=logits, dims=(B, N, ncls), xp=xp if planes else None,
                 precision=precision, x5p=(x5p, x5ld, x5off) if c6p else None,
-                W6p=Wp[5] if c6p else None)
+                W6p=Wp[5] if c6p else None, tnet=tnet)
 
 
 def seg_backward(fw, dlogits, dgmax_out=None, out=None):
     """Gradients of the 20 parameters (state_dict order) given dL/dlogits
     (B*N, C) (and optionally dL/dgmax), from the activations of seg_forward.
     `out`: optional list of 20 parameter-shaped tensors written in place."""
+    return _backward(fw, dlogits, dgmax_out, out)
+
+
+def segregu_backward(fw, dlogits, dgmax_out=None, out=None, reg=None):
+    """Gradients of the 44 parameters (state_dict order) from the activations
+    of segregu_forward.  reg(T, dT): called once dT (B, 128, 128) holds the
+    transform's own gradient, to add what else reaches trans_feat (the
+    orthogonality regulariser, or an upstream gradient), before fstn's
+    backward reads it.
+
+    The gradient at x3 has three consumers: fc1 (the concatenated features),
+    the transform x3 T and fstn.  fc1's part lands in dloc's x3 block masked
+    by its GEMM as before; the other two are summed by pcadv_cloud_xform_bwd
+    (fstn's input gradient rides in as `add`) and masked once as they are
+    accumulated there."""
+    return _backward(fw, dlogits, dgmax_out, out, reg=reg, regu=True)
+
+
+def _backward(fw, dlogits, dgmax_out, out, reg=None, regu=False):
     E = _engine()
+    tn = fw.get("tnet")
+    if regu != (tn is not None):
+        raise ValueError("the activations are not this generator's forward's")
+    o0 = _NTN if regu else 0  # conv1.weight's place in `out`
+    if regu and out is None:
+        out = [torch.empty_like(q) for q in tn["c3"]["p"] + tn["cf"]["p"]] + [None] * 20
     pts, cvec, xloc, gmax, gidx = fw["pts"], fw["cvec"], fw["xloc"], fw["gmax"], fw["gidx"]
     h1, h2, h3, W, Wf = fw["h1"], fw["h2"], fw["h3"], fw["W"], fw["Wf"]
     B, N, ncls = fw["dims"]
@@ -348,8 +477,8 @@ def seg_backward(fw, dlogits, dgmax_out=None, out=None):
     # epilogue (cmask), so each dz is stored masked once and read as is by the
     # weight gradient (which also forms the bias gradient) and the next GEMM.
     def _g(k, like):  # the k-th gradient (state_dict order): caller's buffer or a new one
-        if out is not None:
-            return out[k].view(like.shape) if hasattr(like, "shape") else out[k]
+        if out is not None and out[o0 + k] is not None:
+            return out[o0 + k].view(like.shape) if hasattr(like, "shape") else out[o0 + k]
         return torch.empty_like(like) if hasattr(like, "shape") else torch.empty(like, device=dev)
     # the weight gradients' finishing slab sums wait in this local list and run
     # in one launch at the end (E.finish); an exception drops the list and
@@ -402,13 +531,37 @@ def seg_backward(fw, dlogits, dgmax_out=None, out=None):
         K, O = _CONV[i]
         dWc[i] = _g(2 * i, W[i])
         dbc[i] = _g(2 * i + 1, O)
-        if i > 0:
+        if i == 3 and regu:
+            # conv4 read x3t: its data gradient goes to dx3t (no mask, nothing to add to)
+            x3t, T = tn["x3t"], tn["T"]
+            dx3t = torch.empty(M, 128, device=dev)
+            E.wgrad_and_gemm(fin, (dloc, _LOC, x3t, 128, M, O, K, dWc[i], K),
+                             dict(db=dbc[i], dz_off=_OFF[i]),
+                             E.gemm_desc(dloc, _LOC, W[i], K, dx3t, 128, M, K, O, tb=1,
+                                         precise=pd, a_off=_OFF[i]))
+            dT = torch.empty(B, 128, 128, device=dev)
+            E.xform_bwd(dx3t, 128, xloc, _LOC, T, B, N, 128, dT=dT, x_off=_OFF[2])
+            if reg is not None:
+                reg(T, dT)
+            dx3f = _tnet_backward(tn["cf"], dT, out[12:24], True)
+            E.xform_bwd(dx3t, 128, xloc, _LOC, T, B, N, 128, dx=dloc, lddx=_LOC, add=dx3f,
+                        relu_x=True, x_off=_OFF[2], dx_off=_OFF[2])
+        elif i > 0:
             E.wgrad_and_gemm(fin, (dloc, _LOC, xloc, _LOC, M, O, K, dWc[i], K),
                              dict(db=dbc[i], dz_off=_OFF[i], x_off=_OFF[i - 1]),
                              E.gemm_desc(dloc, _LOC, W[i], K, dloc, _LOC, M, K, O, tb=1,
                                          cmask=xloc, ldm=_LOC, accumulate=True,
                                          precise=pd, a_off=_OFF[i],
                                          m_off=_OFF[i - 1], c_off=_OFF[i - 1]))
+        elif regu:
+            # conv1 read p' = pts T3: dp' = dz1 W1, then dT3 and stn's backward
+            E.wgrad(dloc, _LOC, tn["pin"], 3, M, O, K, dWc[i], K, db=dbc[i], dz_off=_OFF[i],
+                    fin=fin)
+            dpin = torch.empty(M, 3, device=dev)
+            E.gemm(dloc, _LOC, W[0], 3, dpin, 3, M, 3, 64, tb=1, a_off=_OFF[0], precise=pd)
+            dT3 = torch.empty(B, 3, 3, device=dev)
+            E.xform_bwd(dpin, 3, pts, 3, tn["T3"], B, N, 3, dT=dT3)
+            _tnet_backward(tn["c3"], dT3, out[0:12], False)
         else:
             E.wgrad(dloc, _LOC, pts, 3, M, O, K, dWc[i], K, db=dbc[i], dz_off=_OFF[i], fin=fin)
     # every weight gradient's slab sums (collected above) in one launch
@@ -418,6 +571,8 @@ def seg_backward(fw, dlogits, dgmax_out=None, out=None):
     for i in range(6):
         grads += [dWc[i].view(O_shape(i)), dbc[i]]
     grads += [dW1, db1, dW2, db2, dW3, db3, dW4, db4]
+    if regu:
+        grads = [g.view(q.shape) for g, q in zip(out[:_NTN], tn["c3"]["p"] + tn["cf"]["p"])] + grads
     return grads
 
 
@@ -447,6 +602,53 @@ class SegNetFunction(torch.autograd.Function):
         B, N, ncls = ctx.dims
         dl = None if dlogits is None else dlogits.reshape(B * N, ncls)
         return (None, None, None, *seg_backward(fw, dl, dgmax_out))
+
+
+# what segregu_backward reads of segregu_forward's dict, its "tnet" entry and a
+# T-Net's cache (SegReguNetFunction saves and rebuilds them in this order)
+_FW_KEYS = ("pts", "cvec", "xloc", "gmax", "gidx", "h1", "h2", "h3")
+_TN_KEYS = ("T3", "T", "pin", "x3t")
+_TC_KEYS = ("x", "h1", "h2", "g", "gidx", "f1", "f2", "t")
+
+
+class SegReguNetFunction(torch.autograd.Function):
+    """PointNetSeg_regulization forward and its whole backward as one autograd
+    node.  Inputs: pts (B, N, 3), cls (B, 1, 16), then the 44 parameters in
+    state_dict order.  Outputs: logits point-major (B, N, C), gmax (B, 2048),
+    gidx (B, 2048) int32 and T3 (B, 3, 3) (both non-differentiable), trans_feat
+    (B, 128, 128) (differentiable: the regulariser's gradient joins the
+    transform's own before fstn's backward)."""
+
+    @staticmethod
+    def forward(ctx, precision, pts, cls, *params):
+        fw = segregu_forward(pts, cls, [p.detach() for p in params], precision=precision)
+        tn = fw["tnet"]
+        # every tensor the backward reads goes through save_for_backward, flattened
+        # (some are outputs: kept on ctx directly they would tie the node to its
+        # own outputs and nothing would ever be freed); only metadata stays on ctx
+        ctx.save_for_backward(*[fw[n] for n in _FW_KEYS], *fw["W"], *fw["Wf"],
+                              *[tn[n] for n in _TN_KEYS],
+                              *[t for c in (tn["c3"], tn["cf"])
+                                for t in [c[n] for n in _TC_KEYS] + c["p"]])
+        ctx.dims, ctx.precision = fw["dims"], precision
+        ctx.mark_non_differentiable(fw["gidx"], tn["T3"])
+        B, N, ncls = fw["dims"]
+        return fw["logits"].view(B, N, ncls), fw["gmax"], fw["gidx"], tn["T3"], tn["T"]
+
+    @staticmethod
+    def backward(ctx, dlogits, dgmax_out, _dgidx, _dT3, dtrans):
+        t = list(ctx.saved_tensors)
+        take = lambda n: [t.pop(0) for _ in range(n)]  # noqa: E731
+        fw = dict(zip(_FW_KEYS, take(len(_FW_KEYS))), W=take(6), Wf=take(4), dims=ctx.dims,
+                  precision=ctx.precision)
+        tn = dict(zip(_TN_KEYS, take(len(_TN_KEYS))))
+        for name in ("c3", "cf"):
+            tn[name] = dict(zip(_TC_KEYS, take(len(_TC_KEYS))), p=take(12))
+        fw["tnet"] = tn
+        B, N, ncls = fw["dims"]
+        dl = None if dlogits is None else dlogits.reshape(B * N, ncls)
+        reg = None if dtrans is None else (lambda T, dT: dT.add_(dtrans))
+        return (None, None, None, *segregu_backward(fw, dl, dgmax_out, reg=reg))
 
 
 def O_shape(i):
@@ -521,6 +723,49 @@ class PointNetSeg(nn.Module):
     def forward(self, x, cls):
         logits, g, _ = self.forward_points(x, cls)
         return logits.permute(0, 2, 1), g.unsqueeze(2)
+
+
+class PointNetSeg_regulization(nn.Module):
+    """models/pointnet.py:205-259: PointNetSeg with an STN3d on the points and an
+    STNkd(128) on conv3's output.  forward(x: B x N x 3, cls: B x 1 x 16) ->
+    (logits B x NUM_SEG_CLASSES x N, x_global B x 2048 x 1, trans_feat B x 128 x
+    128).  Not a PointNetSeg by type: the steps written for that generator
+    would run this one without its T-Nets.  Under precision="bf16x3" the T-Nets
+    and the two transforms stay on their f32 kernels."""
+
+    def __init__(self, NUM_SEG_CLASSES, *, precision="fp32"):
+        super().__init__()
+        self.output_dim = NUM_SEG_CLASSES
+        self.precision = _check_precision(precision)
+        self.stn = STN3d()
+        self.fstn = STNkd(k=128)
+        self.conv1 = nn.Conv1d(3, 64, 1)
+        self.conv2 = nn.Conv1d(64, 128, 1)
+        self.conv3 = nn.Conv1d(128, 128, 1)
+        self.conv4 = nn.Conv1d(128, 128, 1)
+        self.conv5 = nn.Conv1d(128, 512, 1)
+        self.conv6 = nn.Conv1d(512, 2048, 1)
+        self.fc1 = nn.Linear(3024, 256)
+        self.fc2 = nn.Linear(256, 256)
+        self.fc3 = nn.Linear(256, 128)
+        self.fc4 = nn.Linear(128, self.output_dim)
+
+    def forward_points(self, x, cls):
+        """Point-major logits (B, N, C), x_global (B, 2048), argmax (B, 2048), the
+        input transform T3 (B, 3, 3) and trans_feat (B, 128, 128)."""
+        B, N, c3 = x.shape
+        if c3 != 3:
+            raise ValueError(f"x: expected B x N x 3, got {tuple(x.shape)}")
+        if cls.numel() != B * 16:
+            raise ValueError(f"cls: expected B x 1 x 16, got {tuple(cls.shape)}")
+        _check_dev(x, "x")
+        params = [p for _, p in self.named_parameters()]
+        return SegReguNetFunction.apply(self.precision, x.float().contiguous(),
+                                        cls.float().reshape(B, 1, 16), *params)
+
+    def forward(self, x, cls):
+        logits, g, _, _, trans_feat = self.forward_points(x, cls)
+        return logits.permute(0, 2, 1), g.unsqueeze(2), trans_feat
 
 
 class _SegStep(FusedStep):
@@ -656,11 +901,12 @@ class _SegDiscStep(_SegStep):
     _disc and `losses`, and keeps its own terms in loss_buf[3:]."""
 
     _D_NET = _d_workspace = None
+    _G_NET = PointNetSeg  # the generator's class
 
     def __init__(self, model, model_D, optimizer, optimizer_D, lambda_seg, lambda_adv, lr, lr_D,
                  betas, eps, device, precision, seed, keep_activations):
-        if not isinstance(model, PointNetSeg) or not isinstance(model_D, self._D_NET):
-            raise TypeError(f"{type(self).__name__}: expected a PointNetSeg and a "
+        if not isinstance(model, self._G_NET) or not isinstance(model_D, self._D_NET):
+            raise TypeError(f"{type(self).__name__}: expected a {self._G_NET.__name__} and a "
                             f"{self._D_NET.__name__}")
         if model_D.input_dim != model.output_dim:
             raise ValueError(f"model_D takes {model_D.input_dim} channels, the generator predicts "
@@ -701,7 +947,7 @@ class _SegDiscStep(_SegStep):
         pts = torch.cat([pts_gt, pts_nogt])
         cls_gt = cls_gt.float().reshape(B, 1, 16)
         cls = torch.cat([cls_gt, cls_nogt.float().reshape(B, 1, 16)])
-        fw = seg_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
+        fw = self._g_forward(pts, cls, wpl)
         ncls = fw["dims"][2]
         logits = fw["logits"]
         d = torch.empty(2 * M, ncls, device=self.device)
@@ -714,7 +960,7 @@ class _SegDiscStep(_SegStep):
         d_out = self._disc(logits, ncls, M, N, cls_gt, d, self._ws[1],
                            None if soft_gt is None else soft_gt.reshape(M),
                            None if soft_nogt is None else soft_nogt.reshape(M), semi)
-        seg_backward(fw, d, None, out=self.grad_views)
+        self._g_backward(fw, d)
         if self.keep_activations:
             self.fw, self.d_out = fw, d_out
         if apply_adam:
@@ -724,6 +970,14 @@ class _SegDiscStep(_SegStep):
         """D's fused forward and backward on logits' 2M rows: loss_buf[1:] and D's
         gradients written, the no-GT rows of d filled.  Returns D's output."""
         raise NotImplementedError
+
+    def _g_forward(self, pts, cls, wpl):
+        """The generator's forward on the 2B clouds [GT; no-GT]."""
+        return seg_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
+
+    def _g_backward(self, fw, d):
+        """The generator's backward from dlogits into the flat gradient views."""
+        seg_backward(fw, d, None, out=self.grad_views)
 
     def adam(self):
         """optimizer.step() and optimizer_D.step() (trainer.py:965-966, 1152-1153)."""
@@ -912,3 +1166,44 @@ class SegStackTrainStep(_SegDiscStep):
         if int(self.bad_rows.item()) > 0:
             raise RuntimeError("all elements of input should be between 0 and 1")
         return vals
+
+
+class SegStackReguTrainStep(SegStackTrainStep):
+    """One iteration of run_training_seg_stack_regulization (utils/trainer.py:
+    1244-1363) with PointNetSeg_regulization + StackDiscNet: SegStackTrainStep's
+    launches, with the regularised generator's forward and backward in their
+    places.  Inside the backward, once the feature transform's own gradient is
+    formed, pcadv_tnet_mse_reg adds lambda_regu times the gradient of
+    MSELoss(T T^T, I) of each batch (the 2B clouds as the groups (B, B):
+    trainer.py:1276-1282,1297-1303,1316-1318) and writes the two losses.
+
+    `losses` is [loss_seg, loss_adv, loss_regu, loss_D, loss_D_shape], the
+    order of the reference's log line; loss_regu = l_gt + l_nogt, unscaled.
+    bad_rows, logged() and capture_on are the stack step's."""
+
+    _G_NET = PointNetSeg_regulization
+
+    def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
+                 lambda_adv=0.01, lambda_disc_shape=1.0, lambda_regu=0.001, lr=1e-4, lr_D=1e-4,
+                 betas=(0.9, 0.999), eps=1e-8, device="cuda", precision=None, seed=0,
+                 keep_activations=False):
+        super().__init__(model, model_D, optimizer, optimizer_D, lambda_seg, lambda_adv,
+                         lambda_disc_shape, lr, lr_D, betas, eps, device, precision, seed,
+                         keep_activations)
+        self.lambda_regu = float(lambda_regu)
+        # loss_buf[6:8]: the two batches' regulariser losses, [8]: their sum
+        self.loss_buf = torch.zeros(9, device=self.device)
+        self._loss_idx = torch.tensor([0, 1, 8, 2, 5], device=self.device)
+        self._regu_ws = None  # pcadv_tnet_mse_reg's 4 x (2B) floats, kept between steps
+
+    def _g_forward(self, pts, cls, wpl):
+        return segregu_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
+
+    def _g_backward(self, fw, d):
+        def reg(T, dT):
+            if self._regu_ws is None or self._regu_ws.numel() < 4 * T.shape[0]:
+                self._regu_ws = torch.empty(4 * T.shape[0], device=self.device)
+            _engine().mse_reg(T, T.shape[0] // 2, self.lambda_regu, self.loss_buf[6:8], dT,
+                              ws=self._regu_ws)
+            torch.add(self.loss_buf[6], self.loss_buf[7], out=self.loss_buf[8])
+        segregu_backward(fw, d, None, out=self.grad_views, reg=reg)

@@ -1035,7 +1035,7 @@ def run_testing_seg(dataloader, dataset, model, criterion, logger, test_iter, wr
         pts, cls, seg = data
         pts, cls, seg = pts.float().to(args.device), cls.to(args.device), seg.long().to(args.device)
         with torch.set_grad_enabled(False):
-            pred, _ = model(pts, cls)
+            pred = model(pts, cls)[0]  # (pred, x_global) or (pred, x_global, trans_feat)
             loss = criterion(pred, seg)
         pred_seg = pred.max(1)[1]
         total_accuracy += pred_seg.eq(seg).cpu().numpy().sum() / float(args.input_pts)
@@ -1054,6 +1054,15 @@ def run_testing_seg(dataloader, dataset, model, criterion, logger, test_iter, wr
         writer.add_scalar("IoU/test_cat_iou", mean_cat, test_iter)
         writer.add_scalar("IoU/test_all_iou", mean_all, test_iter)
     return total_accuracy / n, total_loss / n, mean_cat, mean_all
+
+
+def run_testing_seg_regulization(dataloader, dataset, model, criterion, logger, test_iter, writer,
+                                 args):
+    """utils/trainer.py:146-219: run_testing_seg over the 3-tuple model
+    (PointNetSeg_regulization).  The reference's body through the module's
+    forward: the native SegEvaluator covers PointNetSeg only, so this pass
+    never takes it."""
+    return run_testing_seg(dataloader, dataset, model, criterion, logger, test_iter, writer, args)
 
 
 def run_training_pointnet_seg(trainloader_gt, trainloader_gt_iter, testloader, testdataset, model,
@@ -1174,14 +1183,19 @@ def _plain_ce(loss):
 
 
 def _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, pool_gt, pool_nogt,
-                     args, shape_criterion=None):
+                     args, shape_criterion=None, regu_loss=None):
     """The configuration SegAdvTrainStep implements (run_training_seg's fast
     path), or, with a shape_criterion, the one SegStackTrainStep implements
-    (run_training_seg_stack's: StackDiscNet, BCELoss, two plain CrossEntropyLoss)."""
+    (run_training_seg_stack's: StackDiscNet, BCELoss, two plain CrossEntropyLoss);
+    with a regu_loss too, SegStackReguTrainStep's (PointNetSeg_regulization as
+    the generator and a plain MSELoss with mean reduction)."""
     from .discriminator import PointwiseDiscNet, StackDiscNet
-    from .seg import PointNetSeg
+    from .seg import PointNetSeg, PointNetSeg_regulization
     stack = shape_criterion is not None
-    if not (isinstance(model, PointNetSeg)
+    if regu_loss is not None and (type(regu_loss) is not torch.nn.MSELoss
+                                  or regu_loss.reduction != "mean" or not stack):
+        return False
+    if not (isinstance(model, PointNetSeg if regu_loss is None else PointNetSeg_regulization)
             and isinstance(model_D, StackDiscNet if stack else PointwiseDiscNet)):
         return False
     if model_D.input_dim != model.output_dim or str(args.device).split(":")[0] != "cuda":
@@ -1207,28 +1221,40 @@ def _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
 
 def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, pool_gt, pool_nogt,
                   pts, cls, seg, pts_nogt, cls_nogt, args, semi_loss=None, semi=False,
-                  shape_criterion=None):
+                  shape_criterion=None, regu_loss=None):
     """utils/trainer.py:881-966 through autograd over the same modules: returns
     [loss_seg, loss_adv, loss_D].  With a semi_loss, :1956-2061: `semi` is the
     iteration's (args.semi_start > 0 and i_iter > args.semi_start) and the
     values are [loss_seg, loss_adv, loss_semi, loss_D].  With a shape_criterion,
     :1059-1153 (model_D returns (shape logits, D_out); gan_loss is applied to
     D's probability output, so torch's own BCELoss range checks apply): the
-    values are [loss_seg, loss_adv, loss_D, loss_D_shape]."""
+    values are [loss_seg, loss_adv, loss_D, loss_D_shape].  With a regu_loss as
+    well, :1244-1363 (the model returns (pred, x_global, trans_feat);
+    args.lambda_regu x regu_loss(trans_feat trans_feat^T, I) of each batch joins
+    the generator's loss): [loss_seg, loss_adv, loss_regu, loss_D, loss_D_shape],
+    loss_regu the sum of the two batches' values, unscaled."""
     stack = shape_criterion is not None
+
+    def regu(trans):
+        eye = torch.eye(trans.size(1), device=trans.device, dtype=trans.dtype)
+        return regu_loss(torch.bmm(trans, trans.transpose(2, 1)),
+                         eye.unsqueeze(0).repeat(trans.size(0), 1, 1))
     disc = (lambda x: model_D(x)[1]) if stack else model_D
     optimizer.zero_grad()
     optimizer_D.zero_grad()
     for param in model_D.parameters():  # train G
         param.requires_grad = False
-    pred, _ = model(pts, cls)
+    pred, *rest = model(pts, cls)
     l_seg = seg_loss(pred, seg)
     pred_gt_softmax = F.softmax(pred, dim=1)
-    pred_nogt, _ = model(pts_nogt, cls_nogt)
+    pred_nogt, *rest_nogt = model(pts_nogt, cls_nogt)
     pred_nogt_softmax = F.log_softmax(pred_nogt, dim=1)
     D_out = disc(pred_nogt_softmax)
     loss_adv = gan_loss(D_out, make_D_label(input=D_out, value=1, device=args.device, random=False))
     loss = args.lambda_seg * l_seg + args.lambda_adv * loss_adv
+    if regu_loss is not None:
+        l_regu_gt, l_regu_nogt = regu(rest[1]), regu(rest_nogt[1])
+        loss = loss + args.lambda_regu * l_regu_gt + args.lambda_regu * l_regu_nogt
     loss_semi_value = 0.0
     if semi:
         ignore = (D_out <= args.semi_TH).squeeze(1)  # (B N / input_pts, input_pts) on (B, N)
@@ -1256,6 +1282,9 @@ def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, po
         loss_D_value += loss_D.item()
     optimizer.step()  # the reference steps G before D's part: D is frozen there, the same values
     optimizer_D.step()
+    if regu_loss is not None:
+        return [l_seg.item(), loss_adv.item(), l_regu_gt.item() + l_regu_nogt.item(), loss_D_value,
+                loss_D_shape.item()]
     if stack:
         return [l_seg.item(), loss_adv.item(), loss_D_value, loss_D_shape.item()]
     if semi_loss is None:
@@ -1266,7 +1295,7 @@ def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, po
 def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetloader_nogt_iter,
                   testloader, testdataset, model, model_D, gan_loss, seg_loss, optimizer,
                   optimizer_D, history_pool_gt, history_pool_nogt, train_logger, test_logger,
-                  writer, args, semi_loss=None, shape_criterion=None):
+                  writer, args, semi_loss=None, shape_criterion=None, regu_loss=None):
     """The iteration loop shared by run_training_seg (semi_loss None),
     run_training_seg_semi (pseudo-label term from iteration semi_start + 1) and
     run_training_seg_stack (shape_criterion given: StackDiscNet, BCELoss and
@@ -1286,18 +1315,31 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
     shape_criterion (see run_training_seg_stack).  Where the reference loops
     differ, so do these: the fused step's class and condition, the log line,
     the tensorboard tags, and the checkpoint by accuracy that the semi loop does
-    not write; all of it is chosen here, before the loop."""
-    from .seg import SegAdvTrainStep, SegStackTrainStep
+    not write; all of it is chosen here, before the loop.  With a regu_loss as
+    well as a shape_criterion (run_training_seg_stack_regulization) the fused
+    configuration is the stack loop's with PointNetSeg_regulization as the
+    generator and a plain MSELoss (mean) as regu_loss, the step is a
+    SegStackReguTrainStep, the log line gains loss_regu as its fourth field and
+    the test pass is run_testing_seg_regulization."""
+    from .seg import SegAdvTrainStep, SegStackReguTrainStep, SegStackTrainStep
     with_semi, stack = semi_loss is not None, shape_criterion is not None
+    with_regu = regu_loss is not None
     max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
     max_train_epoch = max_train_cat_epoch = max_train_all_epoch = 0
     fusable = _seg_adv_fusable(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                               history_pool_gt, history_pool_nogt, args, shape_criterion) \
+                               history_pool_gt, history_pool_nogt, args, shape_criterion,
+                               regu_loss) \
         and (not with_semi or _semi_fusable(semi_loss))
     step, eager_since = None, False
     tb = getattr(args, "tensorboard", False) and writer is not None
     line = 'iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} '
-    if stack:
+    testing = run_testing_seg_regulization if with_regu else run_testing_seg
+    if with_regu:
+        Step, step_args = SegStackReguTrainStep, dict(lambda_disc_shape=args.lambda_disc_shape,
+                                                      lambda_regu=args.lambda_regu)
+        line += 'loss_regu = {4:.3f} loss_D = {5:.3f} loss_D_shape = {6:.3f} '
+        d_tags = (('Loss/train_D', 3), ('Loss/train_D_shape', 4))  # the reference writes no regu tag
+    elif stack:
         Step, step_args = SegStackTrainStep, dict(lambda_disc_shape=args.lambda_disc_shape)
         line += 'loss_D = {4:.3f} loss_D_shape = {5:.3f} '
         d_tags = (('Loss/train_D', 2), ('Loss/train_D_shape', 3))
@@ -1350,7 +1392,7 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
             vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
                                  history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
                                  cls_nogt, args, semi_loss=semi_loss, semi=semi,
-                                 shape_criterion=shape_criterion)
+                                 shape_criterion=shape_criterion, regu_loss=regu_loss)
         train_logger.info(line.format(i_iter, args.total_iterations, *vals))
         if tb:
             writer.add_scalar('Loss/train_seg', vals[0], i_iter)
@@ -1360,7 +1402,7 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
         if i_iter % args.iter_test_epoch == 0:
             ep = i_iter // args.iter_test_epoch
             save("epoch_{}".format(ep))
-            accu, _, cat_iou, all_iou = run_testing_seg(
+            accu, _, cat_iou, all_iou = testing(
                 dataloader=testloader, dataset=testdataset, model=model, criterion=seg_loss,
                 logger=test_logger, test_iter=i_iter, writer=writer, args=args)
             if max_seg_accu < accu:
@@ -1444,3 +1486,31 @@ def run_training_seg_stack(trainloader_gt, trainloader_nogt, trainloader_gt_iter
                          targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
                          seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
                          train_logger, test_logger, writer, args, shape_criterion=shape_criterion)
+
+
+def run_training_seg_stack_regulization(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                                        targetloader_nogt_iter, testloader, testdataset, model,
+                                        model_D, gan_loss, seg_loss, regu_loss, shape_criterion,
+                                        optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
+                                        train_logger, test_logger, writer, args):
+    """utils/trainer.py:1218-1429: run_training_seg_stack with the regularised
+    generator (PointNetSeg_regulization: an STN3d on the points, an STNkd(128)
+    on conv3's output, trans_feat as the model's third output) and, on both
+    batches, args.lambda_regu x regu_loss(trans_feat trans_feat^T, I) added to
+    the generator's loss.  The log line (loss_regu = l_gt + l_nogt, unscaled, as
+    its fourth field), the tensorboard tags (Loss/train_seg | adv | D | D_shape)
+    and the checkpoints (epoch_{}, best, best_cat_iou, best_all_iou) are the
+    reference's; the test pass is run_testing_seg_regulization.
+
+    With PointNetSeg_regulization + StackDiscNet, two plain Adams, plain
+    CrossEntropyLoss for seg_loss and shape_criterion, BCELoss (mean, no
+    weight), a plain MSELoss (mean) as regu_loss, both pools of size 0 and the
+    HIP device, every iteration whose two batches have the same shape is one
+    SegStackReguTrainStep; anything else, and a ragged last batch, runs the
+    reference's body through autograd over the same modules (_seg_adv_body).
+    A D output outside [0, 1] raises as in run_training_seg_stack."""
+    return _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                         targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
+                         seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
+                         train_logger, test_logger, writer, args, shape_criterion=shape_criterion,
+                         regu_loss=regu_loss)

@@ -851,6 +851,40 @@ size_t pcadv_stackdisc_workspace_bytes(int64_t rows, int max_workgroups);
 int pcadv_stackdisc_forward(const pcadv_stackdisc_args* args, hipStream_t stream);
 int pcadv_stackdisc_backward(const pcadv_stackdisc_args* args, hipStream_t stream);
 
+/* ---- T-Net glue of the regularised seg generator ----------------------------
+ * (PointNetSeg_regulization, models/pointnet.py:205-259;
+ * run_training_seg_stack_regulization, utils/trainer.py:1218-1429.)  Additive
+ * to ABI 11.  Rows are points, point-major; C clouds of Npts points each (any
+ * C, Npts >= 0; zero rows: no launch); k in {3, 128}; T [C][k][k] dense.  Every
+ * sum runs in a fixed order (no atomics): results are bitwise reproducible.
+ * k = 128 on exact f32 MFMAs, k = 3 on VALU FMAs.
+ *
+ * pcadv_cloud_xform_fwd: y[c][n][j] = sum_i x[c][n][i] T[c][i][j]; x has row
+ * stride ldx >= k, y row stride ldy >= k (floats). */
+int pcadv_cloud_xform_fwd(const float* x, int64_t ldx, const float* T, float* y, int64_t ldy,
+                          int C, int Npts, int k, hipStream_t stream);
+
+/* Its backward from dy (row stride lddy), x and T:
+ *   dT[c][i][j] (+)= sum_n x[c][n][i] dy[c][n][j]   (NULL: skipped; accumulate=1 adds)
+ *   dx[c][n][i] += (sum_j dy[c][n][j] T[c][i][j] + add[c][n][i]) * [x[c][n][i] > 0 if relu_x]
+ * dx (NULL: skipped) has row stride lddx and always accumulates; add is a
+ * dense [C*Npts][k] addend or NULL (a second consumer's gradient of x, summed
+ * before the one mask).  With dx and k = 128, T must be 16-byte aligned. */
+int pcadv_cloud_xform_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx,
+                          const float* T, float* dT, int accumulate, float* dx, int64_t lddx,
+                          const float* add, int relu_x, int C, int Npts, int k,
+                          hipStream_t stream);
+
+/* MSELoss()(T T^T, I) per batch (utils/trainer.py:1280-1281,1301-1302): the
+ * first B0 clouds are group 0, the other C - B0 group 1 (B0 = C: one group,
+ * loss[1] = 0).  loss[g] = sum over the group's clouds and i, j of
+ * (T T^T - I)^2 / (B_g k^2); dT[c] += scale (4 / (B_g k^2)) (T_c T_c^T - I) T_c
+ * (dT NULL: loss only; an element whose gradient is 0 is not written, so
+ * T = I leaves dT bitwise as it was).  k = 3 or a multiple of 4 up to 128;
+ * 1 <= B0 <= C; workspace: 4 C floats. */
+int pcadv_tnet_mse_reg(const float* T, int C, int B0, int k, float scale, float* loss, float* dT,
+                       float* workspace, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,13 @@ StackDiscNet(2048, 50, 16)) against the pointwise adversarial step and the
 generator-only step, three graphs on the same 32 clouds and equal generators,
 alternated the same way, with the two discriminators' launches alone, into
 profiles/segstack_bench.json.
+
+--stack --regu times run_training_seg_stack_regulization's step
+(SegStackReguTrainStep with PointNetSeg_regulization(50), fstn's last layer
+scaled so the feature transform starts near the identity) against the stacked
+step of the same run (the conv / fc weights equal, the same 32 clouds and the
+same StackDiscNet weights), alternated the same way, into
+profiles/segregu_bench.json.
 """
 import argparse
 import json
@@ -176,6 +183,60 @@ def _stack(a):
                       "round_spread_us": out["round_spread_us"], "d_alone": out["d_alone"]}))
 
 
+def _regu(a):
+    """--stack --regu: SegStackReguTrainStep against SegStackTrainStep."""
+    import adversarial_learning_on_pointclouds_amd as pc
+    B, N = 16, 2048
+    rng = np.random.default_rng(0)
+    torch.manual_seed(0)
+    pts, cls, seg = _inputs(rng, 2 * B, N)
+    g_regu, g_stack = pc.PointNetSeg_regulization(50).cuda(), pc.PointNetSeg(50).cuda()
+    with torch.no_grad():
+        g_regu.fstn.fc3.weight.mul_(0.02)
+        g_regu.fstn.fc3.bias.mul_(0.02)
+    g_stack.load_state_dict({k: v for k, v in g_regu.state_dict().items()
+                             if not k.startswith(("stn.", "fstn."))})
+    d_regu, d_stack = pc.StackDiscNet(N, 50, 16).cuda(), pc.StackDiscNet(N, 50, 16).cuda()
+    d_stack.load_state_dict(d_regu.state_dict())
+    kw = dict(lr=1e-4, lr_D=1e-4, lambda_adv=0.01, lambda_disc_shape=1.0, seed=5)
+    regu = pc.SegStackReguTrainStep(g_regu, d_regu, lambda_regu=0.001, **kw)
+    stack = pc.SegStackTrainStep(g_stack, d_stack, **kw)
+    halves = (pts[:B].contiguous(), cls[:B].contiguous(), seg[:B].contiguous(),
+              pts[B:].contiguous(), cls[B:].contiguous())
+    graphs = {"regu": regu.capture_on(*halves), "stack": stack.capture_on(*halves)}
+    for g in graphs.values():  # warm-up
+        _time(g, 5)
+    times = {k: [] for k in graphs}
+    for _ in range(a.rounds):
+        for k, g in graphs.items():
+            times[k].append(_time(g, a.steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    diffs = [r - s for r, s in zip(times["regu"], times["stack"])]
+    out = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "steps": a.steps,
+           "what": {"regu": "SegStackReguTrainStep B=16+16 N=2048 fp32, graph replay",
+                    "stack": "SegStackTrainStep B=16+16 N=2048 fp32, graph replay"}}
+    for k in graphs:
+        out[k + "_ms"] = {"median": med[k], "min": min(times[k]), "max": max(times[k]),
+                          "rounds": times[k]}
+    out["regu_over_stack_ms"] = {"median_of_medians": med["regu"] - med["stack"],
+                                 "per_round": diffs, "median": statistics.median(diffs),
+                                 "min": min(diffs), "max": max(diffs)}
+    out["regu_over_stack_share"] = (med["regu"] - med["stack"]) / med["stack"]
+    out["round_spread_us"] = {k: 1e3 * (max(v) - min(v)) for k, v in times.items()}
+    out["losses_last"] = {"regu": [float(x) for x in regu.losses.tolist()],
+                          "stack": [float(x) for x in stack.losses.tolist()]}
+    out["bad_rows_last"] = {"regu": int(regu.bad_rows.item()), "stack": int(stack.bad_rows.item())}
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"regu_ms": med["regu"], "stack_ms": med["stack"],
+                      "regu_over_stack_ms": out["regu_over_stack_ms"]["median"],
+                      "share": out["regu_over_stack_share"],
+                      "round_spread_us": out["round_spread_us"],
+                      "losses_last": out["losses_last"]["regu"]}))
+
+
 def _semi(a):
     """--semi: the adversarial step with run_training_seg_semi's term against
     the same step without it, two graphs over the same inputs and equal models,
@@ -244,15 +305,23 @@ def main():
                     help="time semi=True against semi=False (profiles/segadv_semi_bench.json)")
     ap.add_argument("--stack", action="store_true",
                     help="time SegStackTrainStep against both (profiles/segstack_bench.json)")
+    ap.add_argument("--regu", action="store_true",
+                    help="with --stack: time SegStackReguTrainStep against SegStackTrainStep "
+                         "(profiles/segregu_bench.json)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.regu and not a.stack:
+        ap.error("--regu goes with --stack")
     if a.out is None:
         a.out = os.path.join("profiles", "segadv_semi_bench.json" if a.semi else
+                             "segregu_bench.json" if a.regu else
                              "segstack_bench.json" if a.stack else "segadv_bench.json")
     if not torch.cuda.is_available():
         sys.exit("segadv_bench: no HIP device (the steps are timed on the MI355X only)")
     if a.semi:
         return _semi(a)
+    if a.regu:
+        return _regu(a)
     if a.stack:
         return _stack(a)
     import adversarial_learning_on_pointclouds_amd as pc
