@@ -159,6 +159,16 @@ class StackdiscArgs(ctypes.Structure):
     ]
 
 
+class StepWsLayout(ctypes.Structure):
+    """Mirror of pcadv_step_ws_layout (include/pcadv.h): byte offsets of the
+    step's workspace arrays, a view for tests and diagnostics."""
+
+    _fields_ = [(n, _sz) for n in (
+        "h1", "h2", "logits", "dlogits", "dh2", "dh1", "dgmax",
+        "din", "d1", "d2", "d3", "dd3", "dd2", "dd1",
+        "z4", "z5", "a4", "mask", "dout", "rowloss", "total")]
+
+
 PWD_NONE, PWD_SOFTMAX, PWD_LOG_SOFTMAX = 0, 1, 2
 
 # name -> (restype, argtypes); every symbol of include/pcadv.h
@@ -227,6 +237,7 @@ SIGNATURES = {
     "pcadv_row_eval": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp,
                             _vp, _vp, _sz, _vp]),
     "pcadv_adv_step_workspace_bytes": (_sz, [_i, _i]),
+    "pcadv_adv_step_workspace_layout": (_i, [_i, _i, ctypes.POINTER(StepWsLayout)]),
     "pcadv_adv_step": (_i, [ctypes.POINTER(AdvArgs), _vp]),
     "pcadv_adv_step_adam": (_i, [ctypes.POINTER(AdvArgs), _vp]),
     "pcadv_cls_step": (_i, [ctypes.POINTER(AdvArgs), _vp]),

@@ -848,6 +848,20 @@ int pcadv_row_ce(const float* logits, int64_t ld, const int64_t* labels, int M, 
 
 size_t pcadv_adv_step_workspace_bytes(int B, int N) { return carve(B, N, nullptr).total; }
 
+int pcadv_adv_step_workspace_layout(int B, int N, pcadv_step_ws_layout* out) {
+  PC_REQUIRE(out && B > 0 && B <= 256 && N > 0, "adv_step_workspace_layout: bad B/N or out NULL");
+  // the step's own carve over a nominal base: the offsets are the differences
+  const uintptr_t base = (uintptr_t)1 << 30;
+  const StepWs w = carve(B, N, reinterpret_cast<char*>(base));
+  auto off = [&](const float* p) { return (size_t)(reinterpret_cast<uintptr_t>(p) - base); };
+  *out = pcadv_step_ws_layout{off(w.h1),  off(w.h2),  off(w.logits), off(w.dlogits), off(w.dh2),
+                              off(w.dh1), off(w.dgmax), off(w.din),  off(w.d1),      off(w.d2),
+                              off(w.d3),  off(w.dd3), off(w.dd2),    off(w.dd1),     off(w.z4),
+                              off(w.z5),  off(w.a4),  off(w.mask),   off(w.dout),    off(w.rowloss),
+                              w.total};
+  return PCADV_OK;
+}
+
 int pcadv_adv_step(const pcadv_adv_args* args, hipStream_t stream) { return adv_step(args, stream); }
 
 int pcadv_adv_step_adam(const pcadv_adv_args* args, hipStream_t stream) {

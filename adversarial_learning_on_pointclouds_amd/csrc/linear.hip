@@ -544,9 +544,11 @@ int launch_linear_bwd(const float* dy, const float* y, int act, const float* mas
   // the weight-gradient rows: any number with dz as is (wgrad.h forms), at
   // most 16 MAXC when an activation or dropout applies on the fly
   const bool dz_as_is = act == ACT_NONE && !mask && !step;
-  PC_REQUIRE(M > 0 && N > 0 && K > 0 && K % 4 == 0 && m_w >= 0 && m_w <= M &&
-                 (dz_as_is || !dw || m_w <= 16 * MAXC),
+  PC_REQUIRE(M > 0 && N > 0 && K > 0 && K % 4 == 0 && m_w >= 0 && m_w <= M,
              "linear_bwd: bad shape M=%d m_w=%d N=%d K=%d", M, m_w, N, K);
+  PC_REQUIRE(dz_as_is || !dw || m_w <= 16 * MAXC,
+             "linear_bwd: dw over m_w=%d rows with an activation or dropout applied on the fly "
+             "(at most %d rows)", m_w, 16 * MAXC);
   GemmArgs g{};
   g.x = x; g.w = w; g.dy = dy; g.yact = y; g.act = act;
   g.drop = DropSpec{mask, step, seed, p, 0, 0, 0};

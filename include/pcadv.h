@@ -645,6 +645,43 @@ typedef struct pcadv_adv_args {
 size_t pcadv_adv_step_workspace_bytes(int B, int N);
 int pcadv_adv_step(const pcadv_adv_args* args, hipStream_t stream);
 
+/* A test and diagnostic view of the step's workspace (an addition to ABI 11;
+ * nothing existing changes): the byte offsets, from args->workspace, of the
+ * arrays pcadv_adv_step and pcadv_cls_step called with the same (B, N) leave
+ * there, and `total` = pcadv_adv_step_workspace_bytes(B, N).  The layout is
+ * private to the library and may change with any build: read it through this
+ * call, never by a copy of the offsets (as x_out of pcadv_pwdisc_backward, a
+ * view for tests, not an interface to compute on).  All arrays are f32,
+ * row-major.  With C = 2B generator rows (GT clouds first; the cls step uses
+ * rows [0, B) only) and R = 3B discriminator rows ([D(lsm_gt); D(lsm_nogt);
+ * the adversarial pass on lsm_nogt again]):
+ *   h1 [C][512], h2 [C][256]   fc1 / fc2 outputs (after ReLU and dropout)
+ *   logits, dlogits [C][40]    fc3 output (when args->logits is NULL) and dL/dlogits
+ *   dh2 [C][256], dh1 [C][512] dL/d(fc2 / fc1 pre-activation): each data gradient
+ *                              is stored as the dz of the layer below
+ *   dgmax [C][1024]            dL/d(pooled features) (parts 0..2; part 3 writes
+ *                              args->feat_dgmax instead)
+ *   din [R][40]                the discriminator's input rows (log_softmax)
+ *   d1 [R][512], d2, d3 [R][256]   D conv1..conv3 outputs
+ *   dd1 [R][512], dd2, dd3 [R][256] dL/d(conv1..conv3 pre-activation); rows
+ *                              [0, 2B) carry the D loss, rows [2B, 3B) the
+ *                              generator's adversarial loss
+ *   a4 [2B][64]                D conv4 output, rows [0, 2B) ONLY
+ *   z4, z5 [2B][64]            dL/d(conv4 / conv5 pre-activation), rows [0, 2B)
+ *                              ONLY (the rows D's weight gradients sum over)
+ *   mask [C][256]              the {0,1} dropout mask of fc2 (given or drawn)
+ *   dout [R]                   the D logits
+ *   rowloss [B]                the cls step's CE_r / B
+ * The adversarial step leaves rowloss untouched, the cls step everything from
+ * din to dout but mask.  Returns PCADV_EINVAL for B outside [1, 256], N < 1 or
+ * out NULL. */
+typedef struct {
+  size_t h1, h2, logits, dlogits, dh2, dh1, dgmax;
+  size_t din, d1, d2, d3, dd3, dd2, dd1;
+  size_t z4, z5, a4, mask, dout, rowloss, total;
+} pcadv_step_ws_layout;
+int pcadv_adv_step_workspace_layout(int B, int N, pcadv_step_ws_layout* out);
+
 /* The two Adam updates of pcadv_adv_step alone (optimizer.step() and
  * optimizer_D.step(), trainer.py:558-559), for a step that ran with
  * apply_adam = 0 and whose gradients were then all-reduced across ranks.

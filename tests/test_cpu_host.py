@@ -97,6 +97,54 @@ def test_error_message_roundtrip():
     assert b"bad shape" in lib.pcadv_last_error()
 
 
+def test_linear_bwd_refuses_129_rows_of_on_the_fly_dw():
+    """dw next to an activation or a dropout mask applied on the fly sums at
+    most 128 rows (eight 16-row chunks in registers): m_w = 129 is refused with
+    PCADV_EINVAL and a message on the host, before any launch; with dz as is
+    any m_w <= M passes this check (tests/test_gpu_linear_edges.py runs it)."""
+    import ctypes
+    from adversarial_learning_on_pointclouds_amd import _lib
+    lib = _lib.load()
+    p = lambda k: ctypes.c_void_p(0x100000 * k)  # noqa: E731  (never dereferenced: refused first)
+    M, N, K = 130, 40, 36
+    for act, mask, step in ((1, None, None), (0, p(5), None), (0, None, p(6))):
+        rc = lib.pcadv_linear_bwd(p(1), p(2), act, mask, step, 0, 0.3, p(3), p(4), None, p(7), p(8),
+                                  M, 129, N, K, None)
+        assert rc == -1
+        assert b"at most 128 rows" in lib.pcadv_last_error()
+    assert lib.pcadv_linear_bwd(p(1), p(2), 0, None, None, 0, 0.0, p(3), p(4), None, p(7), p(8), M,
+                                M + 1, N, K, None) == -1
+    assert b"bad shape" in lib.pcadv_last_error()
+
+
+def test_step_workspace_layout_accessor():
+    """pcadv_adv_step_workspace_layout (an addition to ABI 11): offsets taken
+    from the step's own carve: 256-B aligned, ascending in the carve's order,
+    each array's extent inside the next offset, total = the workspace size; bad
+    arguments are refused."""
+    import ctypes
+    from adversarial_learning_on_pointclouds_amd import _lib
+    lib = _lib.load()
+    assert lib.pcadv_abi_version() == 11
+    lay = _lib.StepWsLayout()
+    for B, N in ((1, 16), (6, 16), (256, 16), (32, 1024)):
+        assert lib.pcadv_adv_step_workspace_layout(B, N, ctypes.byref(lay)) == 0
+        assert lay.total == lib.pcadv_adv_step_workspace_bytes(B, N)
+        C, R = 2 * B, 3 * B
+        order = [("h1", C * 512), ("h2", C * 256), ("logits", C * 40), ("dlogits", C * 40),
+                 ("dh2", C * 256), ("dh1", C * 512), ("dgmax", C * 1024), ("din", R * 40),
+                 ("d1", R * 512), ("d2", R * 256), ("d3", R * 256), ("dd3", R * 256),
+                 ("dd2", R * 256), ("dd1", R * 512), ("z4", C * 64), ("z5", C * 64), ("a4", C * 64),
+                 ("mask", C * 256), ("dout", R), ("rowloss", B), ("total", 0)]
+        assert lay.h1 >= C * N * 128 * 4  # x3 comes first (AdvTrainStep.saved_x3)
+        for (a, na), (b, _) in zip(order, order[1:]):
+            assert getattr(lay, a) % 256 == 0
+            assert getattr(lay, a) + 4 * na <= getattr(lay, b), (a, b)
+    for B, N, out in ((0, 16, lay), (257, 16, lay), (4, 0, lay), (4, 16, None)):
+        assert lib.pcadv_adv_step_workspace_layout(B, N, ctypes.byref(out) if out else None) == -1
+        assert b"workspace_layout" in lib.pcadv_last_error()
+
+
 def test_gather_multi_and_epilogue_refuse_bad_arguments():
     """ABI 7's batched gather and iteration epilogue validate on the host before
     any launch (no GPU needed): job counts outside 1..4, a job without its
@@ -265,14 +313,15 @@ def _c_layout(struct, fields, tmp_path):
     return int(out[0]), [int(v) for v in out[1:]]
 
 
-@pytest.mark.parametrize("name", ["AdvArgs", "GatherJob", "PwWgradJob", "PwLayer"])
+@pytest.mark.parametrize("name", ["AdvArgs", "GatherJob", "PwWgradJob", "PwLayer", "StepWsLayout"])
 def test_ctypes_structs_match_the_c_layout(name, tmp_path):
     """The ctypes mirrors of pcadv_adv_args / pcadv_gather_job (the structs
     the trainer fills) have the C structs' size and field offsets."""
     from adversarial_learning_on_pointclouds_amd import _lib
     py = getattr(_lib, name)
     c = {"AdvArgs": "pcadv_adv_args", "GatherJob": "pcadv_gather_job",
-         "PwWgradJob": "pcadv_pw_wgrad_job", "PwLayer": "pcadv_pw_layer"}[name]
+         "PwWgradJob": "pcadv_pw_wgrad_job", "PwLayer": "pcadv_pw_layer",
+         "StepWsLayout": "pcadv_step_ws_layout"}[name]
     fields = [f for f, _ in py._fields_]
     size, offs = _c_layout(c, fields, tmp_path)
     assert ctypes_sizeof(py) == size
