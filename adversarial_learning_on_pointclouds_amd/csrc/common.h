@@ -5,37 +5,12 @@
 #include <cstddef>
 
 #include "../../include/pcadv.h"
+#include "prims.h"
 
 namespace pcadv {
 
 // thread-local last-error text (pcadv_last_error)
 void set_error(const char* fmt, ...);
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// f32 -> three bf16 whose sum is the f32 value (round-to-nearest splits: each
-// residual is exact in f32 and the last one fits 8 significant bits).  Six
-// products of two such splits (l h, m m, h l, m h, h m, h h; the dropped terms
-// are < 2^-23 of |a b|) give an f32-level product on the bf16 matrix pipe.
-__device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
-  hi = (__bf16)v;
-  const float r1 = v - (float)hi;
-  mid = (__bf16)r1;
-  lo = (__bf16)(r1 - (float)mid);
-}
-
-// 32x32x2 f32 MFMA: exact f32 (k-ordered fma chain), 64 cycles / SIMD.
-// lane l supplies A[i=l&31][k=l>>5], B[k=l>>5][j=l&31];
-// D: col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5).
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int acc_row(int r, int lane) {
-  return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-}
 
 // Kernel arguments are read by scalar loads at their first use, and a use that
 // sits behind a branch on another argument costs a further dependent round trip
@@ -134,12 +109,6 @@ __device__ __forceinline__ void load_bfrag(const float* __restrict__ w, int o0, 
   const float* row = w + (size_t)(o0 + r) * K + 4 * h;
 #pragma unroll
   for (int g = 0; g < K / 8; ++g) bfrag[g] = *reinterpret_cast<const f32x4*>(row + 8 * g);
-}
-
-// NaN-propagating "v beats best" (torch.max returns a NaN if one is present;
-// ties keep the earlier index because points arrive in increasing order).
-__device__ __forceinline__ bool beats(float v, float best) {
-  return v > best || (v != v && best == best);
 }
 
 // conv1 (3 -> 64) + ReLU of one point, in the fixed fma order shared by the

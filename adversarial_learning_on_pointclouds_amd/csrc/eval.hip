@@ -42,15 +42,6 @@ struct RowEval {
   int32_t* part_iou;  // [workgroup][EV_MAXP][I, U]
 };
 
-// "candidate (ov, oi) replaces (v, i)": the larger value, a NaN over a number
-// (np.argmax and torch.max return the first NaN), the lower index on a tie.
-__device__ __forceinline__ bool ev_wins(float ov, int oi, float v, int i) {
-  const bool on = ov != ov, vn = v != v;
-  if (on != vn) return on;
-  if (on || ov == v) return oi < i;
-  return ov > v;
-}
-
 // metric.get_iou from a cloud's counts: a part absent from both counts 1, the
 // parts summed in order from 0.0 and divided by their number (np.mean over
 // fewer than 8 values is that sequential sum), so the f64 result is the host's.
@@ -94,7 +85,7 @@ __device__ __forceinline__ void ev_finish_acc(const RowEval& a, int nblk, int la
     ok += a.part_ok[b];
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // wave_sum (prims.h) of the two, interleaved
     s += __shfl_xor(s, o);
     ok += __shfl_xor(ok, o);
   }
@@ -159,12 +150,12 @@ __global__ void __launch_bounds__(EV_T) k_row_eval(const RowEval a) {
     int bi = c0;
 #pragma unroll
     for (int j = 1; j < 4; ++j)
-      if (ev_wins(v[j], c0 + j, bv, bi)) bv = v[j], bi = c0 + j;
+      if (ranks_before(v[j], c0 + j, bv, bi)) bv = v[j], bi = c0 + j;
 #pragma unroll
     for (int o = EV_LPR / 2; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o, EV_LPR);
       const int oi = __shfl_xor(bi, o, EV_LPR);
-      if (ev_wins(ov, oi, bv, bi)) bv = ov, bi = oi;
+      if (ranks_before(ov, oi, bv, bi)) bv = ov, bi = oi;
     }
     float e = 0.f;
 #pragma unroll

@@ -33,11 +33,6 @@ constexpr int SL_DW1 = 0, SL_DB1 = 192, SL_DW2 = 256, SL_DB2 = 4352, SL_DW3 = 44
 constexpr int SZ3 = 130;      // LDS stride of 128-wide rows (= 2 mod 32: 16x16x4 row reads
 constexpr int SZ2 = 66;       //  and 32x32x2 column reads are both conflict-free)
 
-typedef float f32x4m __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4m mfma16(float a, float b, f32x4m c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 constexpr int BW_G = 12;      // hit groups of the dZ3 gather: half-waves of waves 2-7 (4 columns per lane)
 constexpr int BW_RBG = (BW_RB + BW_G - 1) / BW_G;  // batch rows per gather group (mask / combine)
 constexpr int BW_GD = 8;      // W4 rows in flight per gather lane
@@ -633,7 +628,7 @@ k_feat_bwd_chunk(const float* __restrict__ dg, const int32_t* __restrict__ gidx,
 
     // ---- c. dX2 = dZ3 W3 (32 x 128 . 128 x 64), 16x16 tile per wave ---------
     {
-      f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       if (16 * rt < nb) {
         const float* ap = L.dz3 + (16 * rt + r16) * SZ3 + q;
 #pragma unroll
@@ -652,7 +647,7 @@ k_feat_bwd_chunk(const float* __restrict__ dg, const int32_t* __restrict__ gidx,
 
     // ---- d. dX1 = dZ2 W2 (32 x 64 . 64 x 64), 16x16 tile per wave -----------
     {
-      f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       if (16 * rt < nb) {
         const float* ap = L.dz2 + (16 * rt + r16) * SZ2 + q;
 #pragma unroll

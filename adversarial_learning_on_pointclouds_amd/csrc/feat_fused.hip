@@ -31,10 +31,6 @@
 
 namespace pcadv {
 
-__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 // ============================================================================
 // k_point_mlp: conv1..conv3
 // ============================================================================
@@ -191,7 +187,7 @@ k_point_mlp(const float* __restrict__ pts_a, const float* __restrict__ pts_b, in
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         __bf16 a, m, l;
-        split3(j < 4 ? w3raw[2 * kb][j] : w3raw[2 * kb + 1][j - 4], a, m, l);
+        split_planes<3>(j < 4 ? w3raw[2 * kb][j] : w3raw[2 * kb + 1][j - 4], a, m, l);
         w3h[kb][j] = a;
         w3m[kb][j] = m;
         w3l[kb][j] = l;
@@ -264,7 +260,7 @@ k_point_mlp(const float* __restrict__ pts_a, const float* __restrict__ pts_b, in
         float v = acc[i] + bias2;
         v = v > 0.f ? v : 0.f;
         const int row = 32 * pt + acc_row(i, lane);
-        split3(v, L.x2[0][row * X2S + col], L.x2[1][row * X2S + col], L.x2[2][row * X2S + col]);
+        split_planes<3>(v, L.x2[0][row * X2S + col], L.x2[1][row * X2S + col], L.x2[2][row * X2S + col]);
       }
     }
     __syncthreads();
@@ -363,8 +359,6 @@ constexpr int C4_P = 64;    // points per step
 constexpr int C4_G2_MAXC = 63;  // the largest cloud count run in the two-group (G2) form
 constexpr int C4_SB = 136;  // bf16 row stride of the x3 hi / lo tiles (272 B: conflict-free b128 reads)
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int C4_WS = 132;  // f32 row stride of the prologue's W4 staging (conflict-free b128 reads)
 union C4Lds {
   alignas(16) __bf16 x[2][2][2 * C4_P * C4_SB];  // x3 tiles [buffer][hi, lo], up to 128 rows
@@ -372,19 +366,9 @@ union C4Lds {
 };
 
 
-// Screening keys: the f32 value mapped to an order-preserving int32 whose low
-// 6 bits are replaced by 63 - (the point's row inside its 64-point step, less
-// the lane-half offset 4 h), so v_max_i32 / v_med3_i32 keep the top-2 (value,
-// row) of a lane with the lower row first on equal truncated values.  The 6
-// dropped bits (2^-17 relative) only order the candidates, which the exact
-// re-evaluation then ranks by their f32 values; NaN maps above +inf as
-// torch.max ranks it.
-__device__ __forceinline__ int screen_key(float v, int lowc) {
-  const int b = __float_as_int(v);
-  const int ord = b ^ ((b >> 31) & 0x7fffffff);  // int order == float order
-  return (ord & ~63) | lowc;
-}
-// The same key in three instructions (hipcc spends four): t = sign smear;
+// Screening keys (prims.h, screen_key<6>): the row is the point's inside its
+// 64-point step, less the lane-half offset 4 h.
+// The key in three instructions (hipcc spends four on screen_key): t = sign smear;
 // x = b ^ (t & 0x7fffffc0) (order-preserving except in the low bits, which
 // are replaced); key = (x & ~63) | LOWC.  v_bitop3 table index = 4 S0 + 2 S1 + S2.
 // Only for accumulators whose MFMAs retired several instructions earlier
@@ -414,42 +398,6 @@ __device__ __forceinline__ void screen_seq(const f32x16& acc, int m_ord, int m_h
   (screen_one<I0 + J, TOP2>(acc, m_ord, m_hi, k1, k2), ...);
 }
 __device__ __forceinline__ int key_row(int k) { return 31 - (k & 63); }
-__device__ __forceinline__ float key_value(int k) {
-  const int ord = k & ~63;
-  return __int_as_float(ord ^ ((ord >> 31) & 0x7fffffff));
-}
-constexpr int KEY_NONE = (int)0x80000000;  // below every real key
-
-// Sum over the 32 lanes of each half-wave, the total in every lane of the half
-// (DPP quad / half-row / row mirrors, then one swizzle across the two rows);
-// every lane adds the same operands, so all get bitwise the same total.
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// Sum over each octet of lanes (8 k .. 8 k + 7), the total in all eight
-__device__ __forceinline__ float octet_sum(float v) {
-  v += dpp<0xB1>(v);   // quad_perm [1,0,3,2]: xor 1
-  v += dpp<0x4E>(v);   // quad_perm [2,3,0,1]: xor 2
-  v += dpp<0x141>(v);  // row_half_mirror: lane i <- 7 - i within 8 (the other quad)
-  return v;
-}
-__device__ __forceinline__ float half_sum(float v) {
-  v += dpp<0xB1>(v);   // quad_perm [1,0,3,2]: xor 1
-  v += dpp<0x4E>(v);   // quad_perm [2,3,0,1]: xor 2
-  v += dpp<0x141>(v);  // row_half_mirror: lane i <- 7 - i within 8 (the other quad)
-  v += dpp<0x140>(v);  // row_mirror: lane i <- 15 - i within 16 (the other 8)
-  v += __shfl_xor(v, 16);
-  return v;
-}
-
-// (va, ia) ranks before (vb, ib): larger value, NaN above all, lower index on ties
-__device__ __forceinline__ bool ranks_before(float va, int ia, float vb, int ib) {
-  const bool na = va != va, nb = vb != vb;
-  if (na || nb) return na && (!nb || ia < ib);
-  return va > vb || (va == vb && ia < ib);
-}
-
 // Merge one step's top-2 keys (n1 >= n2, both tagged with step u) into the
 // running top-2 (r1 >= r2, tags t1, t2) of earlier steps.  Keys of different
 // steps compare by their truncated value only (the low bits are rows within a
@@ -639,7 +587,7 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
     for (int i = 2 * kb_lo; i < 2 * kb_hi; ++i) {
       if constexpr (decltype(MASKED)::value)
         if (u * 32 + acc_row(i, lane) >= N) continue;
-      const int key = screen_key(acc[i], 31 - acc_row(i, 0));
+      const int key = screen_key<6>(acc[i], 32 + acc_row(i, 0));  // low bits 31 - row: key_row
       if constexpr (NP4 == 3) k2 = max(min(key, k1), k2);  // median(key, k1, k2): v_med3_i32
       k1 = max(k1, key);
     }
@@ -824,7 +772,7 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
     const int i2 = t2 < 0 ? 0x7fffffff : t2 * 32 + key_row(r2) + hm;
     const int j1 = u1 < 0 ? 0x7fffffff : u1 * 32 + key_row(o1) + ho;
     const int j2 = u2 < 0 ? 0x7fffffff : u2 * 32 + key_row(o2) + ho;
-    float v1 = t1 < 0 ? -INFINITY : key_value(r1), v2 = t2 < 0 ? -INFINITY : key_value(r2);
+    float v1 = t1 < 0 ? -INFINITY : key_value<6>(r1), v2 = t2 < 0 ? -INFINITY : key_value<6>(r2);
     int a1 = i1, a2 = i2;
     if (ranks_before(v2, a2, v1, a1)) {  // equal truncated values: order by index
       const float tv = v1;
@@ -833,7 +781,7 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
       a1 = i2;
       a2 = i1;
     }
-    const float w1v = u1 < 0 ? -INFINITY : key_value(o1), w2v = u2 < 0 ? -INFINITY : key_value(o2);
+    const float w1v = u1 < 0 ? -INFINITY : key_value<6>(o1), w2v = u2 < 0 ? -INFINITY : key_value<6>(o2);
     // insert (w1v, j1) and (w2v, j2)
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -985,9 +933,6 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
 struct C4W16 {};  // form tag
 constexpr int C4W_T = 1024;
 
-__device__ __forceinline__ f32x4 mfma16_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 // LDS row slot of point p of a step: rows 0-3 and 12-15 of a tile in the even
 // slots, rows 4-11 in the odd ones (the ds_read_b128 lane groups pair exactly
 // these row sets of neighbouring lane quarters)
@@ -1114,7 +1059,7 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
 #pragma unroll
     for (int v = v0; v < v0 + cnt; ++v) {
       const int row = 16 * ((2 * pp + (v >> 2)) & 3) + (v & 3);
-      const int key = screen_key(acc[pp & 1][v >> 2][v & 3], 63 - row);
+      const int key = screen_key<6>(acc[pp & 1][v >> 2][v & 3], row);
       k2 = max(min(key, k1), k2);  // median(key, k1, k2) for k2 <= k1: v_med3_i32
       k1 = max(k1, key);
     }
@@ -1228,7 +1173,7 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
   auto key_row64 = [](int k) { return 63 - (k & 63); };
   int a1 = t1 < 0 ? 0x7fffffff : t1 * 64 + key_row64(r1) + hm;
   int a2 = t2 < 0 ? 0x7fffffff : t2 * 64 + key_row64(r2) + hm;
-  float v1 = t1 < 0 ? -INFINITY : key_value(r1), v2 = t2 < 0 ? -INFINITY : key_value(r2);
+  float v1 = t1 < 0 ? -INFINITY : key_value<6>(r1), v2 = t2 < 0 ? -INFINITY : key_value<6>(r2);
   if (ranks_before(v2, a2, v1, a1)) {  // equal truncated values: order by index
     const float tv = v1;
     v1 = v2;

@@ -37,23 +37,10 @@ constexpr int GM_BM = 128, GM_BN = 128, GM_BK = 32;
 constexpr int GM_T = 256;   // 4 waves, 2 x 2, each 64 x 64 of C
 constexpr int GM_S = 40;    // bf16 row stride of the staged tiles (80 B: conflict-free b128 reads)
 
-typedef __bf16 bf16x8g __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4g __attribute__((ext_vector_type(4)));
-
 struct GemmLds {
   alignas(16) __bf16 a[3][GM_BM * GM_S];  // [hi, (mid,) lo][m][k]
   alignas(16) __bf16 b[3][GM_BN * GM_S];  // [hi, (mid,) lo][n][k]
 };
-
-// f32 -> NPL bf16 planes summing to it (round-to-nearest splits): NPL = 2
-// (hi, lo: 16 significant bits) or 3 (hi, mid, lo: the whole f32 significand)
-template <int NPL>
-__device__ __forceinline__ void split_planes(float v, __bf16 (&o)[3]) {
-  o[0] = (__bf16)v;
-  const float r1 = v - (float)o[0];
-  o[1] = (__bf16)r1;
-  if (NPL == 3) o[2] = (__bf16)(r1 - (float)o[1]);
-}
 
 struct GemmP {
   const float* a; long long lda;
@@ -81,23 +68,9 @@ struct GemmP {
   const __bf16* bp[3]; long long ldbp;
   __bf16* cp[2]; long long ldcp;    // nullable: the epilogue also writes C's hi / lo planes
   // max-over-points screening epilogue (mode 2): per (row tile, column) top-2
+  // (screen_key<7> of the row within the 128-row tile)
   int2* part;                      // [M / BM][N] screening keys
 };
-
-__device__ __forceinline__ f32x16 mfma_bf16g(bf16x8g a, bf16x8g b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// screening keys (as k_conv4_max, feat_fused.hip): the f32 value as an
-// order-preserving int32 with 127 - (row within the 128-row tile) in the low
-// 7 bits, so v_max_i32 / v_med3_i32 keep the top-2 (value, row), lower row
-// first on equal truncated values
-__device__ __forceinline__ int gkey(float v, int row) {
-  const int b = __float_as_int(v);
-  const int ord = b ^ ((b >> 31) & 0x7fffffff);
-  return (ord & ~127) | (127 - row);
-}
-constexpr int GKEY_NONE = (int)0x80000000;
 
 // NP = 3: three products of hi/lo splits (relative error <= ~1.2e-5 of
 // sum|a b|); NP = 6: six products of hi/mid/lo splits (h h, h m, m h, h l, m m,
@@ -132,15 +105,15 @@ __device__ __forceinline__ void epilogue_rows_plain(const GemmP& p, float* C, co
         if (p.relu) v[t] = v[t] > 0.f ? v[t] : 0.f;
       *reinterpret_cast<f32x4*>(dst) = v;
       if (p.cp[0]) {  // the hi / lo planes the next layer stages (ldcp % 4 == 0)
-        bf16x4g hv, lv;
+        bf16x4 hv, lv;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           hv[t] = (__bf16)v[t];
           lv[t] = (__bf16)(v[t] - (float)hv[t]);
         }
         const size_t pofs = (size_t)m * p.ldcp + n;
-        *reinterpret_cast<bf16x4g*>(p.cp[0] + pofs) = hv;
-        *reinterpret_cast<bf16x4g*>(p.cp[1] + pofs) = lv;
+        *reinterpret_cast<bf16x4*>(p.cp[0] + pofs) = hv;
+        *reinterpret_cast<bf16x4*>(p.cp[1] + pofs) = lv;
       }
     } else {
 #pragma unroll
@@ -232,15 +205,15 @@ __device__ __forceinline__ void epilogue_rows(const GemmP& p, float* C, const fl
       }
       *reinterpret_cast<f32x4*>(dst) = v;
       if (p.cp[0]) {  // the hi / lo planes the next layer stages (ldcp % 4 == 0)
-        bf16x4g hv, lv;
+        bf16x4 hv, lv;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           hv[t] = (__bf16)v[t];
           lv[t] = (__bf16)(v[t] - (float)hv[t]);
         }
         const size_t pofs = (size_t)m * p.ldcp + n;
-        *reinterpret_cast<bf16x4g*>(p.cp[0] + pofs) = hv;
-        *reinterpret_cast<bf16x4g*>(p.cp[1] + pofs) = lv;
+        *reinterpret_cast<bf16x4*>(p.cp[0] + pofs) = hv;
+        *reinterpret_cast<bf16x4*>(p.cp[1] + pofs) = lv;
       }
     } else {  // ragged right edge or unaligned output: element by element
       const float* br = p.bias_rows ? p.bias_rows + (size_t)(m / p.rows_per_group) * p.N + n : nullptr;
@@ -385,35 +358,35 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
   };
   auto store_rows = [&](const f32x4 (&v)[4], __bf16 (*planes)[GM_BM * GM_S]) {
     const int row = tid >> 1, kk = 16 * (tid & 1);
-    bf16x8g pv[3][2];
+    bf16x8 pv[3][2];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       __bf16 o[3];
-      split_planes<NPL>(v[j >> 2][j & 3], o);
+      split_planes<NPL>(v[j >> 2][j & 3], o[0], o[1], o[2]);
 #pragma unroll
       for (int q = 0; q < NPL; ++q) pv[q][j >> 3][j & 7] = o[q];
     }
 #pragma unroll
     for (int q = 0; q < NPL; ++q) {
-      *reinterpret_cast<bf16x8g*>(&planes[q][row * GM_S + kk]) = pv[q][0];
-      *reinterpret_cast<bf16x8g*>(&planes[q][row * GM_S + kk + 8]) = pv[q][1];
+      *reinterpret_cast<bf16x8*>(&planes[q][row * GM_S + kk]) = pv[q][0];
+      *reinterpret_cast<bf16x8*>(&planes[q][row * GM_S + kk + 8]) = pv[q][1];
     }
   };
   auto store_cols = [&](const f32x4 (&v)[4], __bf16 (*planes)[GM_BM * GM_S]) {
     const int col = 4 * (tid >> 3), kk = 4 * (tid & 7);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      bf16x4g pv[3];
+      bf16x4 pv[3];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         __bf16 o[3];
-        split_planes<NPL>(v[j][i], o);
+        split_planes<NPL>(v[j][i], o[0], o[1], o[2]);
 #pragma unroll
         for (int q = 0; q < NPL; ++q) pv[q][j] = o[q];
       }
 #pragma unroll
       for (int q = 0; q < NPL; ++q)
-        *reinterpret_cast<bf16x4g*>(&planes[q][(col + i) * GM_S + kk]) = pv[q];
+        *reinterpret_cast<bf16x4*>(&planes[q][(col + i) * GM_S + kk]) = pv[q];
     }
   };
   // planes: thread = (row tid >> 1, 16 k at 16 (tid & 1)); v[0..1] = hi, v[2..3]
@@ -469,15 +442,15 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
   auto mfma_tile = [&]() {
 #pragma unroll
     for (int kb = 0; kb < GM_BK / 16; ++kb) {
-      bf16x8g fa[3][2], fb[3][2];  // [plane][tile]
+      bf16x8 fa[3][2], fb[3][2];  // [plane][tile]
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int ar = (64 * wm + 32 * t + r) * GM_S + 16 * kb + 8 * h;
         const int br = (64 * wn + 32 * t + r) * GM_S + 16 * kb + 8 * h;
 #pragma unroll
         for (int q = 0; q < NPL; ++q) {
-          fa[q][t] = *reinterpret_cast<const bf16x8g*>(&L.a[q][ar]);
-          fb[q][t] = *reinterpret_cast<const bf16x8g*>(&L.b[q][br]);
+          fa[q][t] = *reinterpret_cast<const bf16x8*>(&L.a[q][ar]);
+          fb[q][t] = *reinterpret_cast<const bf16x8*>(&L.b[q][br]);
         }
       }
 #pragma unroll
@@ -485,16 +458,16 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           if constexpr (NP == 6) {  // smallest terms first
-            acc[i][j] = mfma_bf16g(fa[2][i], fb[0][j], acc[i][j]);
-            acc[i][j] = mfma_bf16g(fa[1][i], fb[1][j], acc[i][j]);
-            acc[i][j] = mfma_bf16g(fa[0][i], fb[2][j], acc[i][j]);
-            acc[i][j] = mfma_bf16g(fa[1][i], fb[0][j], acc[i][j]);
-            acc[i][j] = mfma_bf16g(fa[0][i], fb[1][j], acc[i][j]);
-            acc[i][j] = mfma_bf16g(fa[0][i], fb[0][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[2][i], fb[0][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[1][i], fb[1][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[0][i], fb[2][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[1][i], fb[0][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[0][i], fb[1][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[0][i], fb[0][j], acc[i][j]);
           } else {
-            acc[i][j] = mfma_bf16g(fa[1][i], fb[0][j], acc[i][j]);
-            acc[i][j] = mfma_bf16g(fa[0][i], fb[1][j], acc[i][j]);
-            acc[i][j] = mfma_bf16g(fa[0][i], fb[0][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[1][i], fb[0][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[0][i], fb[1][j], acc[i][j]);
+            acc[i][j] = mfma_bf16(fa[0][i], fb[0][j], acc[i][j]);
           }
         }
     }
@@ -528,7 +501,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
       }
     };
     // one k-block's fragments: [plane][tile] of A and B (32 VGPRs)
-    auto read_kb = [&](int buf, int kb, bf16x8g (&fa)[2][2], bf16x8g (&fb)[2][2]) {
+    auto read_kb = [&](int buf, int kb, bf16x8 (&fa)[2][2], bf16x8 (&fb)[2][2]) {
       const int c = 2 * kb + h;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -537,23 +510,23 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
         const int ob = rb_ * GM_BK + 8 * (c ^ ((rb_ >> 2) & 3));
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-          fa[q][t] = *reinterpret_cast<const bf16x8g*>(gl + (size_t)(buf * 4 + q) * PL + oa);
-          fb[q][t] = *reinterpret_cast<const bf16x8g*>(gl + (size_t)(buf * 4 + 2 + q) * PL + ob);
+          fa[q][t] = *reinterpret_cast<const bf16x8*>(gl + (size_t)(buf * 4 + q) * PL + oa);
+          fb[q][t] = *reinterpret_cast<const bf16x8*>(gl + (size_t)(buf * 4 + 2 + q) * PL + ob);
         }
       }
     };
-    auto mfma_kb = [&](const bf16x8g (&fa)[2][2], const bf16x8g (&fb)[2][2]) {
+    auto mfma_kb = [&](const bf16x8 (&fa)[2][2], const bf16x8 (&fb)[2][2]) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = mfma_bf16g(fa[1][i], fb[0][j], acc[i][j]);
-          acc[i][j] = mfma_bf16g(fa[0][i], fb[1][j], acc[i][j]);
-          acc[i][j] = mfma_bf16g(fa[0][i], fb[0][j], acc[i][j]);
+          acc[i][j] = mfma_bf16(fa[1][i], fb[0][j], acc[i][j]);
+          acc[i][j] = mfma_bf16(fa[0][i], fb[1][j], acc[i][j]);
+          acc[i][j] = mfma_bf16(fa[0][i], fb[0][j], acc[i][j]);
         }
     };
     const int nt = (kz1 - kz0) / GM_BK;
-    bf16x8g fa0[2][2], fb0[2][2], fa1[2][2], fb1[2][2];
+    bf16x8 fa0[2][2], fb0[2][2], fa1[2][2], fb1[2][2];
     issue(kz0, 0);
     __syncthreads();
     if (nt > 1) issue(kz0 + GM_BK, 1);
@@ -609,14 +582,14 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, int lin, int gx, in
     __shared__ int2 red[2][GM_BN];  // the two wm halves of each column
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      int k1 = GKEY_NONE, k2 = GKEY_NONE;
+      int k1 = KEY_NONE, k2 = KEY_NONE;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int row = 64 * wm + 32 * i + acc_row(e, lane);
           if (m0 + row < Mlim) {
-            const int key = gkey(acc[i][j][e], row);
+            const int key = screen_key<7>(acc[i][j][e], row);
             k2 = max(min(key, k1), k2);
             k1 = max(k1, key);
           }
@@ -811,23 +784,23 @@ k_gemm_bf2_big(GemmP p) {
   auto mfma_tile = [&](int buf) {
 #pragma unroll
     for (int kb = 0; kb < GM_BK / 16; ++kb) {
-      bf16x8g fb[2][2];  // [plane][j]
+      bf16x8 fb[2][2];  // [plane][j]
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int br = (64 * wn + 32 * j + r) * GM_S + 16 * kb + 8 * h;
 #pragma unroll
-        for (int q = 0; q < 2; ++q) fb[q][j] = *reinterpret_cast<const bf16x8g*>(&L.op[buf].b[q][br]);
+        for (int q = 0; q < 2; ++q) fb[q][j] = *reinterpret_cast<const bf16x8*>(&L.op[buf].b[q][br]);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int ar = (128 * wm + 32 * i + r) * GM_S + 16 * kb + 8 * h;
-        const bf16x8g ah = *reinterpret_cast<const bf16x8g*>(&L.op[buf].a[0][ar]);
-        const bf16x8g al = *reinterpret_cast<const bf16x8g*>(&L.op[buf].a[1][ar]);
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(&L.op[buf].a[0][ar]);
+        const bf16x8 al = *reinterpret_cast<const bf16x8*>(&L.op[buf].a[1][ar]);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = mfma_bf16g(al, fb[0][j], acc[i][j]);
-          acc[i][j] = mfma_bf16g(ah, fb[1][j], acc[i][j]);
-          acc[i][j] = mfma_bf16g(ah, fb[0][j], acc[i][j]);
+          acc[i][j] = mfma_bf16(al, fb[0][j], acc[i][j]);
+          acc[i][j] = mfma_bf16(ah, fb[1][j], acc[i][j]);
+          acc[i][j] = mfma_bf16(ah, fb[0][j], acc[i][j]);
         }
       }
     }
@@ -857,31 +830,31 @@ k_gemm_bf2_big(GemmP p) {
       }
     };
     // fragments of one 16-deep k-block (48 VGPRs): B [j][plane], A [i][plane]
-    auto read_kb = [&](int buf, int kb, bf16x8g (&fa)[4][2], bf16x8g (&fb)[2][2]) {
+    auto read_kb = [&](int buf, int kb, bf16x8 (&fa)[4][2], bf16x8 (&fb)[2][2]) {
       const int c = 2 * kb + h;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int row = 64 * wn + 32 * j + r;
         const int off = row * GM_BK + 8 * (c ^ ((row >> 2) & 3));
 #pragma unroll
-        for (int q = 0; q < 2; ++q) fb[j][q] = *reinterpret_cast<const bf16x8g*>(&G.op[buf].b[q][off]);
+        for (int q = 0; q < 2; ++q) fb[j][q] = *reinterpret_cast<const bf16x8*>(&G.op[buf].b[q][off]);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = 128 * wm + 32 * i + r;
         const int off = row * GM_BK + 8 * (c ^ ((row >> 2) & 3));
 #pragma unroll
-        for (int q = 0; q < 2; ++q) fa[i][q] = *reinterpret_cast<const bf16x8g*>(&G.op[buf].a[q][off]);
+        for (int q = 0; q < 2; ++q) fa[i][q] = *reinterpret_cast<const bf16x8*>(&G.op[buf].a[q][off]);
       }
     };
-    auto mfma_kb = [&](const bf16x8g (&fa)[4][2], const bf16x8g (&fb)[2][2]) {
+    auto mfma_kb = [&](const bf16x8 (&fa)[4][2], const bf16x8 (&fb)[2][2]) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = mfma_bf16g(fa[i][1], fb[j][0], acc[i][j]);
-          acc[i][j] = mfma_bf16g(fa[i][0], fb[j][1], acc[i][j]);
-          acc[i][j] = mfma_bf16g(fa[i][0], fb[j][0], acc[i][j]);
+          acc[i][j] = mfma_bf16(fa[i][1], fb[j][0], acc[i][j]);
+          acc[i][j] = mfma_bf16(fa[i][0], fb[j][1], acc[i][j]);
+          acc[i][j] = mfma_bf16(fa[i][0], fb[j][0], acc[i][j]);
         }
     };
     // two LDS buffers, one barrier per tile, placed between the tile's two
@@ -890,7 +863,7 @@ k_gemm_bf2_big(GemmP p) {
     // barrier earlier), so tile t + 2's DMA goes into that buffer and tile
     // t + 1's fragments are read while k-block 1 of tile t multiplies
     const int nt = K / GM_BK;
-    bf16x8g fa0[4][2], fb0[2][2], fa1[4][2], fb1[2][2];
+    bf16x8 fa0[4][2], fb0[2][2], fa1[4][2], fb1[2][2];
     issue(0, 0);
     __syncthreads();
     if (nt > 1) issue(GM_BK, 1);
@@ -942,14 +915,14 @@ k_gemm_bf2_big(GemmP p) {
     const int t128 = 2 * (tx % T2) + wm;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      int k1 = GKEY_NONE, k2 = GKEY_NONE;
+      int k1 = KEY_NONE, k2 = KEY_NONE;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int row = 32 * i + acc_row(e, lane);
           if (GL || m0 + 128 * wm + row < Mlim) {  // GL: whole tiles, every row is in range
-            const int key = gkey(acc[i][j][e], row);
+            const int key = screen_key<7>(acc[i][j][e], row);
             k2 = max(min(key, k1), k2);  // median(key, k1, k2) for k2 <= k1
             k1 = max(k1, key);
           }
@@ -1349,27 +1322,6 @@ k_colsum_fin(const float* __restrict__ part, int nchunk, int N, float* __restric
 // the bias and the ReLU before the max (pointnet.py:301-303: relu(conv6) then
 // torch.max).  Eight lanes per row (octet DPP sums), as k_conv4_max's tail.
 // ---------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dppg(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float octet_sum_g(float v) {
-  v += dppg<0xB1>(v);
-  v += dppg<0x4E>(v);
-  v += dppg<0x141>(v);
-  return v;
-}
-
-__device__ __forceinline__ bool rank_before_g(float va, int ia, float vb, int ib) {
-  const bool na = va != va, nb = vb != vb;
-  if (na || nb) return na && (!nb || ia < ib);
-  return va > vb || (va == vb && ia < ib);
-}
-__device__ __forceinline__ float gkey_value(int k) {
-  const int ord = k & ~127;
-  return __int_as_float(ord ^ ((ord >> 31) & 0x7fffffff));
-}
-
 // one wave per 8 (cloud, channel) pairs; x rows [C*Npts][K] (row stride ldx)
 __global__ void __launch_bounds__(256)
 k_max_combine(const int2* __restrict__ part, int T, int Npts, int C, int O,
@@ -1389,11 +1341,11 @@ k_max_combine(const int2* __restrict__ part, int T, int Npts, int C, int O,
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int key = q ? kk.y : kk.x;
-        if (key == GKEY_NONE) continue;
-        const float v = gkey_value(key);
+        if (key == KEY_NONE) continue;
+        const float v = key_value<7>(key);
         const int idx = t * GM_BM + 127 - (key & 127);
-        const bool a = rank_before_g(v, idx, v1, i1);
-        const bool b = !a && rank_before_g(v, idx, v2, i2);
+        const bool a = ranks_before(v, idx, v1, i1);
+        const bool b = !a && ranks_before(v, idx, v2, i2);
         const float nv2 = a ? v1 : (b ? v : v2);
         const int ni2 = a ? i1 : (b ? idx : i2);
         v1 = a ? v : v1;
@@ -1412,8 +1364,8 @@ k_max_combine(const int2* __restrict__ part, int T, int Npts, int C, int O,
     for (int q = 0; q < 2; ++q) {
       const float v = q ? a2 : a1;
       const int idx = q ? j2 : j1;
-      const bool a = rank_before_g(v, idx, v1, i1);
-      const bool b = !a && rank_before_g(v, idx, v2, i2);
+      const bool a = ranks_before(v, idx, v1, i1);
+      const bool b = !a && ranks_before(v, idx, v2, i2);
       const float nv2 = a ? v1 : (b ? v : v2);
       const int ni2 = a ? i1 : (b ? idx : i2);
       v1 = a ? v : v1;
@@ -1445,13 +1397,13 @@ k_max_combine(const int2* __restrict__ part, int T, int Npts, int C, int O,
       }
     }
   }
-  e1 = octet_sum_g(e1);
-  e2 = octet_sum_g(e2);
+  e1 = octet_sum(e1);
+  e2 = octet_sum(e2);
   if (valid && part_lane == 0) {
     const float bb = bias ? bias[o] : 0.f;
     e1 += bb;
     e2 += bb;
-    const bool second = near && rank_before_g(e2, i2, e1, i1);
+    const bool second = near && ranks_before(e2, i2, e1, i1);
     float g = second ? e2 : e1;
     if (relu) g = g > 0.f ? g : 0.f;
     gmax[(size_t)c * O + o] = g;
@@ -2243,7 +2195,7 @@ k_row_ce_wave(const float* __restrict__ logits, long long ld, const int64_t* __r
     const float* x = logits + (size_t)m * ld;
     const int y = (int)labels[m];
     const float v = lane < Ccls ? x[lane] : -INFINITY;
-    float mx = v;
+    float mx = v;  // wave_max, wave_sum (prims.h), written out
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     float e = lane < Ccls ? expf(v - mx) : 0.f;

@@ -34,12 +34,6 @@ enum DropMode { DM_NONE = 0, DM_MASK = 1, DM_RNG = 2 };
 
 static int drop_mode(const DropSpec& d) { return d.mask ? DM_MASK : (d.step ? DM_RNG : DM_NONE); }
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4v mfma16(float a, float b, f32x4v c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 enum Op { OP_FWD = 0, OP_BWD_DATA = 1, OP_BWD_WEIGHT = 2 };
 
 struct GemmArgs {
@@ -131,9 +125,9 @@ __device__ __forceinline__ void load_ab(const GemmArgs& g, int r0, int c0, int r
     // out[m][n] = sum_k x[m][k] w[n][k]  (K % 4 == 0: kk < K covers all four)
     const int m = r0 + r, n = c0 + r;
     const bool va = cv && m < g.M && kk < g.K, vb = cv && n < g.N && kk < g.K;
-    const f32x4v av = *reinterpret_cast<const f32x4v*>(
+    const f32x4 av = *reinterpret_cast<const f32x4*>(
         g.x + (size_t)(va ? m : 0) * g.K + (va ? kk : 0));
-    const f32x4v bv = *reinterpret_cast<const f32x4v*>(
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(
         g.w + (size_t)(vb ? n : 0) * g.K + (vb ? kk : 0));
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -146,7 +140,7 @@ __device__ __forceinline__ void load_ab(const GemmArgs& g, int r0, int c0, int r
     if (ACT == ACT_NONE && DM == DM_NONE && (g.N & 3) == 0) {
       // dz stored as is (the producer applied the masks): one 16-B load
       const bool va = cv && m < g.M && kk < g.N;
-      const f32x4v av = *reinterpret_cast<const f32x4v*>(
+      const f32x4 av = *reinterpret_cast<const f32x4*>(
           g.dy + (size_t)(va ? m : 0) * g.N + (va ? kk : 0));
 #pragma unroll
       for (int j = 0; j < 4; ++j) a[j] = va ? av[j] : 0.f;
@@ -180,9 +174,9 @@ __device__ __forceinline__ void load_ab(const GemmArgs& g, int r0, int c0, int r
 // Chunks past nch load clamped addresses and contribute zeros, so the loop is
 // branch-free and every load is issued before the first MFMA.
 template <int OP, int NC, int ACT, int DM>
-__device__ __forceinline__ f32x4v wave_tile(const GemmArgs& g, int r0, int c0, int k0, int nch,
+__device__ __forceinline__ f32x4 wave_tile(const GemmArgs& g, int r0, int c0, int k0, int nch,
                                             int lane, uint32_t step, float* asum,
-                                            f32x4v acc = {0.f, 0.f, 0.f, 0.f}) {
+                                            f32x4 acc = {0.f, 0.f, 0.f, 0.f}) {
   const int r = lane & 15, q = lane >> 4;
   float a[NC][4], b[NC][4];
 #pragma unroll
@@ -220,26 +214,26 @@ constexpr int BT_S = 20;                // LDS row stride (floats): conflict-fre
 constexpr int BT_WAVE = 16 * SPLITC * BT_S;
 constexpr int BT_MAXS = 8;              // waves per block with an LDS region
 template <int NC>
-__device__ __forceinline__ f32x4v wave_tile_bdt(const GemmArgs& g, int r0, int c0, int k0, int nch,
-                                                int lane, float* bt, f32x4v acc) {
+__device__ __forceinline__ f32x4 wave_tile_bdt(const GemmArgs& g, int r0, int c0, int k0, int nch,
+                                                int lane, float* bt, f32x4 acc) {
   const int r = lane & 15, q = lane >> 4;
   const int m = r0 + r;
   float a[NC][4];
-  f32x4v wv[NC];
+  f32x4 wv[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int kk = k0 + 16 * c + 4 * q;
     const bool va = c < nch && m < g.M && kk < g.N;
-    const f32x4v av = *reinterpret_cast<const f32x4v*>(g.dy + (size_t)(va ? m : 0) * g.N +
+    const f32x4 av = *reinterpret_cast<const f32x4*>(g.dy + (size_t)(va ? m : 0) * g.N +
                                                        (va ? kk : 0));
 #pragma unroll
     for (int j = 0; j < 4; ++j) a[c][j] = va ? av[j] : 0.f;
     // W rows n = k0 + 16c + lane/4, columns c0 + 4 (lane & 3) .. + 3
     const int n = k0 + 16 * c + (lane >> 2), kc = c0 + 4 * (lane & 3);
     const bool vb = c < nch && n < g.N && kc < g.K;
-    const f32x4v w = *reinterpret_cast<const f32x4v*>(g.w + (size_t)(vb ? n : 0) * g.K +
+    const f32x4 w = *reinterpret_cast<const f32x4*>(g.w + (size_t)(vb ? n : 0) * g.K +
                                                       (vb ? kc : 0));
-    wv[c] = vb ? w : f32x4v{0.f, 0.f, 0.f, 0.f};
+    wv[c] = vb ? w : f32x4{0.f, 0.f, 0.f, 0.f};
   }
 #ifdef PCADV_STAMPS
   asm volatile("" ::: "memory");
@@ -249,7 +243,7 @@ __device__ __forceinline__ f32x4v wave_tile_bdt(const GemmArgs& g, int r0, int c
 #endif
 #pragma unroll
   for (int c = 0; c < NC; ++c)
-    *reinterpret_cast<f32x4v*>(bt + (16 * c + (lane >> 2)) * BT_S + 4 * (lane & 3)) = wv[c];
+    *reinterpret_cast<f32x4*>(bt + (16 * c + (lane >> 2)) * BT_S + 4 * (lane & 3)) = wv[c];
   // the wave's own lanes read what the others wrote
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -276,7 +270,7 @@ __device__ void split_job(const GemmArgs& g, int tile, int rows, int cols, int R
   const int r0 = (tile / ctiles) * 16, c0 = (tile % ctiles) * 16;
   const int k0 = wave * L;
   // a slice longer than 16 * SPLITC (reductions > 1024) runs in rounds
-  f32x4v acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int base = 0; base < L; base += 16 * SPLITC) {
     const int kb = k0 + base;
     int nch = 0;
@@ -333,7 +327,7 @@ __device__ void split_job(const GemmArgs& g, int tile, int rows, int cols, int R
     const int nt = (g.chain_n + 15) / 16, r = lane & 15;
     if (wave < nt) {
       const int j = 16 * wave + r;
-      f32x4v acc2 = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) {
         const int k = 4 * s4 + q;
@@ -371,7 +365,7 @@ __device__ void weight_job(const GemmArgs& g, int tile, int ntiles_total) {
   const int nch = (g.m_w + 15) / 16;
   float s;
   // the load count follows the chunk count (m_w <= 64 at B = 32: half the loads)
-  const f32x4v acc = nch <= MAXC / 2
+  const f32x4 acc = nch <= MAXC / 2
                          ? wave_tile<OP_BWD_WEIGHT, MAXC / 2, ACT, DM>(g, r0, c0, 0, nch, lane, step, &s)
                          : wave_tile<OP_BWD_WEIGHT, MAXC, ACT, DM>(g, r0, c0, 0, nch, lane, step, &s);
   const int col = lane & 15, q = lane >> 4;

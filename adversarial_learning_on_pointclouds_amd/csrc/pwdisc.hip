@@ -180,12 +180,6 @@ __device__ __forceinline__ void pwd_chain3(const PwdNet& p, float* x0, float* x1
   __syncthreads();
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // conv4 + activation of the tile x3 into y4 [64][PD_S4] (wave = 32 of the 128
 // channels, both row tiles), a barrier, then the max over the channels, first
 // index on ties: 4 lanes x 32 channels per row (row = tid >> 2).  All four
@@ -807,8 +801,7 @@ __global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int 
     for (int t = lane; t < G; t += 64)
       bad += (int)__hip_atomic_load(part + (size_t)4 * G + t, __ATOMIC_RELAXED,
                                     __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) bad += __shfl_xor(bad, o2);
+    bad = wave_sum(bad);
   }
   __syncthreads();
   if (tid < 2 * S) (tid < S ? o.db5 : o.dw5)[tid < S ? tid : tid - S] = fin[4 + tid];

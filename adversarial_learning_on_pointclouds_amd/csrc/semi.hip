@@ -46,15 +46,6 @@ struct RowSemi {
   int32_t* part_k;
 };
 
-// "candidate (ov, oi) replaces (v, i)": k_row_eval's order (the larger value, a
-// NaN over a number, the lower index on a tie).
-__device__ __forceinline__ bool sm_wins(float ov, int oi, float v, int i) {
-  const bool on = ov != ov, vn = v != v;
-  if (on != vn) return on;
-  if (on || ov == v) return oi < i;
-  return ov > v;
-}
-
 // One row by its sixteen lanes: the lane's four logits in v, the row's maximum
 // bv and its first index bi, and es = the sum of exp(x - max) over the classes
 // OTHER than bi (that one is exp(0) = 1 exactly), so the row's loss is
@@ -74,12 +65,12 @@ __device__ __forceinline__ void sm_row(const float* x, int c0, int ncls, float (
   bi = c0;
 #pragma unroll
   for (int j = 1; j < 4; ++j)
-    if (sm_wins(v[j], c0 + j, bv, bi)) bv = v[j], bi = c0 + j;
+    if (ranks_before(v[j], c0 + j, bv, bi)) bv = v[j], bi = c0 + j;
 #pragma unroll
   for (int o = SM_LPR / 2; o > 0; o >>= 1) {
     const float ov = __shfl_xor(bv, o, SM_LPR);
     const int oi = __shfl_xor(bi, o, SM_LPR);
-    if (sm_wins(ov, oi, bv, bi)) bv = ov, bi = oi;
+    if (ranks_before(ov, oi, bv, bi)) bv = ov, bi = oi;
   }
   es = 0.f;
 #pragma unroll
@@ -150,7 +141,7 @@ __global__ void __launch_bounds__(SM_T) k_row_semi_apply(const RowSemi a) {
     n += b < nblk ? a.part_k[b] : 0;
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // wave_sum (prims.h) of the two, interleaved
     s += __shfl_xor(s, o);
     n += __shfl_xor(n, o);
   }

@@ -36,8 +36,6 @@ struct SemiArgs {           // run_training_semi's pseudo-label term (k_head_bwd
 };
 constexpr int TW = TT / 64;
 
-typedef float f32x4t __attribute__((ext_vector_type(4)));
-
 #ifdef PCADV_STAMPS
 // diagnostic build only: phase timestamps (s_memrealtime) [kernel][block][16]
 __device__ uint64_t g_tail_stamps[3][16][16];
@@ -45,9 +43,6 @@ __device__ uint64_t g_tail_stamps[3][16][16];
 #else
 #define TSTAMP(kern, k) do { } while (0)
 #endif
-__device__ __forceinline__ f32x4t mfma16t(float a, float b, f32x4t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 enum BMode { B_OK = 0, B_KO = 1 };  // B[k][j] = W[j * ldw + k]  |  W[k * ldw + j]
 
@@ -98,9 +93,9 @@ __device__ __forceinline__ void rows_layer(const float* A, int as, const float* 
       av[s] = vk ? a : 0.f;
     }
     __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead of the MFMA chain
-    f32x4t acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = 0; s < NS; ++s) acc = mfma16t(av[s], bv[s], acc);
+    for (int s = 0; s < NS; ++s) acc = mfma16(av[s], bv[s], acc);
     if (C == 1) {
       if (j < NC) {
         const float bj = bias ? bias[j] : 0.f;
@@ -252,7 +247,7 @@ k_head_fwd(const float* __restrict__ h2, const float* __restrict__ w3, const flo
   {
     const int row = wave, m = r0 + row;
     const float v = lane < 40 ? L.lg[row * 44 + lane] : -INFINITY;
-    float mx = v;
+    float mx = v;  // wave_max, wave_sum (prims.h), written out
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     const float e = lane < 40 ? expf(v - mx) : 0.f;
@@ -278,9 +273,7 @@ k_head_fwd(const float* __restrict__ h2, const float* __restrict__ w3, const flo
   }
   __syncthreads();
   if (sp == 0 && wave == 0) {  // the block's CE sum: a fixed butterfly over wave 0
-    float s = lane < TR ? L.rl[lane] : 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float s = wave_sum(lane < TR ? L.rl[lane] : 0.f);
     if (lane == 0) lpart[rb] = s;
   }
   // D conv1 on the GT rows (D rows [0,B)) and noGT rows (D rows [B,2B) and,
@@ -403,7 +396,7 @@ k_disc_tail(const float* __restrict__ d3, int B, const float* __restrict__ w4,
   }
   if (tid < 64) {  // the block's three loss sums: a fixed butterfly over wave 0 (lanes >= TR add 0)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int o = 32; o > 0; o >>= 1) {  // wave_sum (prims.h) of the three, interleaved
       l0 += __shfl_xor(l0, o);
       l1 += __shfl_xor(l1, o);
       l2 += __shfl_xor(l2, o);
@@ -445,8 +438,8 @@ k_disc_tail(const float* __restrict__ d3, int B, const float* __restrict__ w4,
     if (m < 2 * B) {
       const float* src = arr == 0 ? L.z4 : (arr == 1 ? L.z5 : L.a4);
       float* dst = arr == 0 ? z4g : (arr == 1 ? z5g : a4g);
-      *reinterpret_cast<f32x4t*>(dst + (size_t)m * 64 + 4 * c4) =
-          *reinterpret_cast<const f32x4t*>(src + row * 68 + 4 * c4);
+      *reinterpret_cast<f32x4*>(dst + (size_t)m * 64 + 4 * c4) =
+          *reinterpret_cast<const f32x4*>(src + row * 68 + 4 * c4);
     }
   }
   float* slab = slabs + (size_t)blockIdx.x * DT_SLAB_LD;
@@ -476,6 +469,7 @@ k_disc_tail(const float* __restrict__ d3, int B, const float* __restrict__ w4,
 //   no-GT logits next to the adversarial one.
 __device__ __forceinline__ void wave_argmax40(float v, int lane, float& mx, int& am) {
   // (value, index) max over the lanes < 40, lower index on equal values
+  // (not ranks_before: no NaN rule; a NaN logit has already made the step's losses NaN)
   float bv = lane < 40 ? v : -INFINITY;
   int bi = lane < 40 ? lane : 64;
 #pragma unroll
@@ -494,9 +488,7 @@ __device__ __forceinline__ void wave_argmax40(float v, int lane, float& mx, int&
 __device__ __forceinline__ int semi_kept(const float* dout, int B, float th, int lane) {
   int c = 0;
   for (int j = lane; j < B; j += 64) c += dout[2 * B + j] > th ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  return c;
+  return wave_sum(c);
 }
 struct HeadBwdLds {
   float w1[512 * 48];          // discriminator conv1 weight [512][40], rows padded to 48
@@ -526,7 +518,7 @@ k_head_bwd(const float* __restrict__ dz1, const float* __restrict__ h2,
     constexpr int TK = 3;  // 40 columns in 3 tiles
     if (t >= 32 * TK) return;
     const int o0 = 16 * (t / TK), k0 = 16 * (t % TK), r = lane & 15, q = lane >> 4;
-    f32x4t acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float s = 0.f;
     for (int m0 = 0; m0 < C; m0 += 16) {
       float a[4], b[4];
@@ -543,7 +535,7 @@ k_head_bwd(const float* __restrict__ dz1, const float* __restrict__ h2,
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        acc = mfma16t(a[u], b[u], acc);
+        acc = mfma16(a[u], b[u], acc);
         s += a[u];
       }
     }
@@ -650,9 +642,7 @@ k_head_bwd(const float* __restrict__ dz1, const float* __restrict__ h2,
     float dl = 0.f;
     if (m >= B && m < C) {
       const float g = lane < 40 ? L.ddin[row * 44 + lane] : 0.f;
-      float s = g;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+      const float s = wave_sum(g);
       if (lane < 40) dl = g - expf(lsm_or_dl) * s;
       if (semi.on) {
         const int kept = semi_kept(semi.dout, B, semi.th, lane);
@@ -687,9 +677,7 @@ k_head_bwd(const float* __restrict__ dz1, const float* __restrict__ h2,
       float mx;
       int am;
       wave_argmax40(x, lane, mx, am);
-      float e = lane < 40 ? expf(x - mx) : 0.f;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+      const float e = wave_sum(lane < 40 ? expf(x - mx) : 0.f);
       sum += logf(e);  // -log_softmax at the argmax = log sum exp(x - max)
     }
     if (lane == 0) {
@@ -782,7 +770,7 @@ k_cls_head(const float* __restrict__ h2, const float* __restrict__ drop_mask, fl
   {
     const int row = wave;
     const float v = lane < 40 ? L.lg[row * 44 + lane] : -INFINITY;
-    float mx = v;
+    float mx = v;  // wave_max, wave_sum (prims.h), written out
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     const float e = lane < 40 ? expf(v - mx) : 0.f;

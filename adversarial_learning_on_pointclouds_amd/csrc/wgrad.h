@@ -26,14 +26,12 @@ struct WgradJob {
 
 constexpr int WG_MAXC = 8;  // 16-row chunks per slab (128 rows)
 
-typedef float wg_f32x4 __attribute__((ext_vector_type(4)));
-
 // One wave: the (r0, c0) tile over rows [m0, m0 + 16 nch), NC >= nch chunks,
 // accumulated onto acc / *asum; chunks past nch load clamped addresses and
 // contribute zeros, so every load is issued before the first MFMA.
 template <int NC>
-__device__ __forceinline__ wg_f32x4 wgrad_tile(const WgradJob& j, int r0, int c0, int m0, int nch,
-                                               int lane, float* asum, wg_f32x4 acc) {
+__device__ __forceinline__ f32x4 wgrad_tile(const WgradJob& j, int r0, int c0, int m0, int nch,
+                                               int lane, float* asum, f32x4 acc) {
   const int r = lane & 15, q = lane >> 4;
   const int n = r0 + r, k = c0 + r;
   float a[NC][4], b[NC][4];
@@ -55,7 +53,7 @@ __device__ __forceinline__ wg_f32x4 wgrad_tile(const WgradJob& j, int r0, int c0
   for (int c = 0; c < NC; ++c) {
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][jj], b[c][jj], acc, 0, 0, 0);
+      acc = mfma16(a[c][jj], b[c][jj], acc);
       s += a[c][jj];
     }
   }
@@ -65,7 +63,7 @@ __device__ __forceinline__ wg_f32x4 wgrad_tile(const WgradJob& j, int r0, int c0
 
 // the tile's outputs: dw rows r0 + 4 q + jj, column c0 + (lane & 15); db from
 // the lane sums of the 4 lane groups
-__device__ __forceinline__ void wgrad_store(const WgradJob& j, int r0, int c0, wg_f32x4 acc,
+__device__ __forceinline__ void wgrad_store(const WgradJob& j, int r0, int c0, f32x4 acc,
                                             float s, int lane) {
   const int col = lane & 15, q = lane >> 4;
 #pragma unroll
@@ -86,7 +84,7 @@ __device__ __forceinline__ void wgrad_wave(const WgradJob& j, int tile, int lane
   const int ctiles = (j.K + 15) / 16;
   const int r0 = (tile / ctiles) * 16, c0 = (tile % ctiles) * 16;
   float s = 0.f;
-  wg_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int m0 = 0; m0 < j.m_w; m0 += 16 * WG_MAXC) {
     const int nch = min(WG_MAXC, (j.m_w - m0 + 15) / 16);
     // the load count follows the chunk count (m_w <= 64 at B = 32: half the loads)
@@ -122,11 +120,11 @@ __device__ __forceinline__ void wgrad_region(const WgradJob& j, int region, floa
   float* zl = lds;
   float* xl = lds + 16 * WG_MAXC * WGB_ZS;
   constexpr int TPW = WGB_TILES / WGB_MIN_WAVES;  // tiles per wave at most
-  wg_f32x4 acc[TPW];
+  f32x4 acc[TPW];
   float s[TPW];
 #pragma unroll
   for (int i = 0; i < TPW; ++i) {
-    acc[i] = wg_f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     s[i] = 0.f;
   }
   const int r = lane & 15, q = lane >> 4;
@@ -137,30 +135,30 @@ __device__ __forceinline__ void wgrad_region(const WgradJob& j, int region, floa
     // store; pieces past the staged rows issue no load
     constexpr int PZ = 16 * WG_MAXC * (WGB_N / 4) / (64 * WGB_MIN_WAVES);
     constexpr int PX = 16 * WG_MAXC * (WGB_K / 4) / (64 * WGB_MIN_WAVES);
-    wg_f32x4 vz[PZ], vx[PX];
+    f32x4 vz[PZ], vx[PX];
 #pragma unroll
     for (int u = 0; u < PZ; ++u) {
       const int e = tid + u * nthr, m = e >> 4, n = n0 + 4 * (e & 15);
-      vz[u] = wg_f32x4{0.f, 0.f, 0.f, 0.f};
+      vz[u] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (m < rows && m0 + m < j.m_w && n < j.N)
-        vz[u] = *reinterpret_cast<const wg_f32x4*>(j.dz + (size_t)(m0 + m) * j.N + n);
+        vz[u] = *reinterpret_cast<const f32x4*>(j.dz + (size_t)(m0 + m) * j.N + n);
     }
 #pragma unroll
     for (int u = 0; u < PX; ++u) {
       const int e = tid + u * nthr, m = e >> 3, k = k0 + 4 * (e & 7);
-      vx[u] = wg_f32x4{0.f, 0.f, 0.f, 0.f};
+      vx[u] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (m < rows && m0 + m < j.m_w && k < j.K)
-        vx[u] = *reinterpret_cast<const wg_f32x4*>(j.x + (size_t)(m0 + m) * j.K + k);
+        vx[u] = *reinterpret_cast<const f32x4*>(j.x + (size_t)(m0 + m) * j.K + k);
     }
 #pragma unroll
     for (int u = 0; u < PZ; ++u) {
       const int e = tid + u * nthr, m = e >> 4;
-      if (m < rows) *reinterpret_cast<wg_f32x4*>(zl + m * WGB_ZS + 4 * (e & 15)) = vz[u];
+      if (m < rows) *reinterpret_cast<f32x4*>(zl + m * WGB_ZS + 4 * (e & 15)) = vz[u];
     }
 #pragma unroll
     for (int u = 0; u < PX; ++u) {
       const int e = tid + u * nthr, m = e >> 3;
-      if (m < rows) *reinterpret_cast<wg_f32x4*>(xl + m * WGB_XS + 4 * (e & 7)) = vx[u];
+      if (m < rows) *reinterpret_cast<f32x4*>(xl + m * WGB_XS + 4 * (e & 7)) = vx[u];
     }
     __syncthreads();
 #pragma unroll
@@ -178,7 +176,7 @@ __device__ __forceinline__ void wgrad_region(const WgradJob& j, int region, floa
         }
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], b[jj], acc[i], 0, 0, 0);
+          acc[i] = mfma16(a[jj], b[jj], acc[i]);
           s[i] += a[jj];
         }
       }
