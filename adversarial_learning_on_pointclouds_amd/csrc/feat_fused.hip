@@ -426,7 +426,7 @@ __device__ __forceinline__ void pair_merge(int n1, int u1, int n2, int u2, int& 
 // NP4: conv4's bf16 products per f32 product: 3 (f32-level screening + the exact
 // f32 re-evaluation of the top two, the default) or 1 (bf16 mode: x3 and W4
 // rounded to bf16, f32 accumulate; the screened winner is the result, no
-// re-evaluation: gmax carries the 2^-17 key truncation).
+// re-evaluation: gmax carries the 2^-17 key truncation, toward zero).
 // G2: fewer than 64 clouds leave CUs idle with 256-channel workgroups, so a
 // workgroup takes 128 channels (8 per cloud) and its two wave groups (waves
 // 0-3, 4-7: the same 32-channel blocks) screen alternate 32-point units of the
@@ -833,7 +833,11 @@ k_conv4_max(const float* __restrict__ x3g, int C, int N, const float* __restrict
     // DESIGN.md, Numerics.)
     if constexpr (NP4 == 1) {  // bf16 mode: the screened winner and its value
       if (h == 0) {
-        float gv = v1 + b4[o];
+        // key_value gives a negative value back with its six dropped bits
+        // set (the floor of the key's order, which is what the ranking above
+        // needs); the result carries them cleared, as a positive value does,
+        // so a value that lost only zero bits comes back exactly
+        float gv = __int_as_float(__float_as_int(v1) & ~63) + b4[o];
         int gi = a1;
         if (relu && gv <= 0.f) gv = 0.f, gi = 0;  // see below
         gmax[(size_t)c * C4_O + o] = gv;

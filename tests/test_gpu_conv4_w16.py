@@ -7,11 +7,14 @@ buffer reused).
 
 On small integers every split product and partial sum is exact and the key
 truncation drops only zero bits, so gmax / gidx must equal numpy's max and
-first argmax with no tolerance.  Runs on an MI355X only."""
+first argmax with no tolerance.  The generator of the integer case is
+tests/feat_fwd_cases.py's (w16_integer_case), which also holds the cases of the
+other eight forms (tests/test_gpu_feat_fwd_edges.py).  Runs on an MI355X only."""
 import numpy as np
 import pytest
 import torch
 
+import feat_fwd_cases as fc
 from oracle import pointnet_np as onp
 
 pytestmark = pytest.mark.gpu
@@ -27,51 +30,9 @@ def _t(a, dtype=torch.float32):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dtype)
 
 
-def _positions(kind, N, rng):
-    """Point indices of one distinct row, by where its equal values sit."""
-    T = int(rng.integers(0, N // 16))   # a 16-point tile
-    U = int(rng.integers(0, N // 64))   # a 64-point span
-    S = int(rng.integers(0, N // 128))  # a 128-point step
-    r = [int(v) for v in rng.integers(0, 4, 4)]
-    if kind == 0:  # one tile, rows of different lane quarters (4 q + reg)
-        q = rng.permutation(4)
-        return [16 * T + 4 * int(q[0]) + r[0], 16 * T + 4 * int(q[1]) + r[1],
-                16 * T + 4 * int(q[2]) + r[2]]
-    if kind == 1:  # different tiles of one span
-        t = rng.permutation(4)
-        return [64 * U + 16 * int(t[0]) + 4 * r[0] + r[1], 64 * U + 16 * int(t[1]) + 4 * r[2] + r[3],
-                64 * U + 16 * int(t[2]) + 4 * r[1] + r[0]]
-    if kind == 2:  # both spans of a step, the later span's copy in the lower row
-        return [128 * S + 64 + 16 * r[0] + 4 * r[1] + r[2], 128 * S + 16 * r[1] + 4 * r[3] + 3]
-    # different steps (N = 128 has one: two spans then)
-    s = rng.permutation(max(N // 128, 2))
-    return [(128 * int(s[0]) + 16 * r[0] + 4 * r[1] + r[2]) % N,
-            (128 * int(s[1]) + 64 + 16 * r[2] + 4 * r[3] + r[0]) % N]
-
-
-def _integer_case(N, seed):
-    """C clouds of small integers in [-4, 4], each built from five distinct
-    rows: a filler f and two pairs f +- d, f +- e (so the filler, their
-    midpoint, never beats both of a pair and the pooled point is one of the
-    few placed rows, at most of the 1024 channels); W4 and the bias too."""
-    rng = np.random.default_rng(seed)
-    W = rng.integers(-4, 5, (1024, 128)).astype(np.float32)
-    b = rng.integers(-4, 5, 1024).astype(np.float32)
-    x = np.empty((C, N, 128), np.float32)
-    gmax = np.empty((C, 1024), np.float32)
-    gidx = np.empty((C, 1024), np.int64)
-    for c in range(C):
-        f = rng.integers(-2, 3, 128)
-        d, e = rng.integers(-2, 3, 128), rng.integers(-2, 3, 128)
-        rows = np.stack([f, f + d, f - d, f + e, f - e]).astype(np.float32)
-        which = np.zeros(N, np.int64)
-        for k in range(1, 5):
-            which[_positions((c + k) % 4, N, rng)] = k
-        x[c] = rows[which]
-        v = (rows.astype(np.float64) @ W.astype(np.float64).T + b)[which]  # exact: |v| < 2^12
-        gmax[c] = v.max(0)
-        gidx[c] = v.argmax(0)  # the first index of the maximum
-    return x, W, b, gmax, gidx
+# the integer case (five distinct rows per cloud, equal values planted by
+# structural position) lives with the other forms' generators
+_integer_case = fc.w16_integer_case
 
 
 @pytest.fixture(scope="module", params=[128, 256, 384])
