@@ -159,6 +159,20 @@ class StackdiscArgs(ctypes.Structure):
     ]
 
 
+class DualTailArgs(ctypes.Structure):
+    """Mirror of pcadv_dual_tail_args (include/pcadv.h)."""
+
+    _fields_ = [
+        ("y", _vp), ("C", _i), ("n0", _i64), ("n1", _i64),
+        ("out", _vp), ("argc", _vp), ("losses", _vp),
+        ("soft0", _vp), ("soft1", _vp), ("soft_out", _vp),
+        ("rng_seed", _u64), ("step_count", _vp),
+        ("dout_d", _vp), ("dout_adv", _vp), ("lambda_adv", _f),
+        ("dz_d", _vp), ("dz_adv", _vp), ("max_workgroups", _i),
+        ("workspace", _vp), ("workspace_bytes", _sz),
+    ]
+
+
 class StepWsLayout(ctypes.Structure):
     """Mirror of pcadv_step_ws_layout (include/pcadv.h): byte offsets of the
     step's workspace arrays, a view for tests and diagnostics."""
@@ -254,6 +268,13 @@ SIGNATURES = {
     "pcadv_cloud_xform_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i, _i, _i,
                                    _i, _vp]),
     "pcadv_tnet_mse_reg": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "pcadv_dual_input": (_i, [_vp, _i64, _i, _i64, _i64, _i, _i, _vp, _vp]),
+    "pcadv_dual_input_bwd": (_i, [_vp, _vp, _i, _i64, _i, _vp, _i64, _vp]),
+    "pcadv_lrelu_fwd": (_i, [_vp, _i64, _vp]),
+    "pcadv_lrelu_bwd": (_i, [_vp, _vp, _i64, _vp]),
+    "pcadv_dual_point_tail_workspace_bytes": (_sz, [_i64]),
+    "pcadv_dual_point_tail": (_i, [ctypes.POINTER(DualTailArgs), _vp]),
+    "pcadv_sgd": (_i, [_vp, _vp, _vp, _i64, _f, _vp]),
 }
 
 _lib = None

@@ -14,7 +14,15 @@ run_training_seg_stack (utils/trainer.py:1028-1216): the same four layers with
 LeakyReLU(0.2), the max over the 128 channels, conv5 = Conv1d(1, num_shapes, 1)
 on that one value per point (the shape logits) and disc_out = lse / (lse + 1)
 with lse their logsumexp; stackdisc_forward / stackdisc_backward call the fused
-kernels (csrc/pwdisc.hip, the k_stk_fwd part)."""
+kernels (csrc/pwdisc.hip, the k_stk_fwd part).
+
+BaseDiscNet, ShapeDiscNet and PointDiscNet (:82-137), the dual discriminator of
+run_training_seg_dual (utils/trainer.py:2123-2382): a shared trunk (50 -> 64 ->
+64 -> 256, LeakyReLU(0.2)), a per-point head (256 -> 256 -> 128 -> 128 and the
+max over the 128 channels) and a shape head (256 -> 512, the max over the
+points, 512 -> 64 -> num_shapes).  Their forward is plain torch on whatever
+device the module is on; the training iteration's native path is
+seg.SegDualTrainStep (the dense GEMM engine and csrc/dualdisc.hip)."""
 from __future__ import annotations
 
 import ctypes
@@ -29,7 +37,8 @@ from .ops import ACT_LRELU, ACT_NONE, LinearFunction
 
 __all__ = ["DeepConvDiscNet", "PointwiseDiscNet", "pwdisc_forward", "pwdisc_backward",
            "pwdisc_workspace", "PWD_NONE", "PWD_SOFTMAX", "PWD_LOG_SOFTMAX", "StackDiscNet",
-           "stackdisc_forward", "stackdisc_backward", "stackdisc_workspace"]
+           "stackdisc_forward", "stackdisc_backward", "stackdisc_workspace", "BaseDiscNet",
+           "ShapeDiscNet", "PointDiscNet"]
 
 PWD_MAX_DIM = 64  # input channels the fused kernels take (the MFMA's padded K)
 STACK_MAX_SHAPES = 32  # shape classes the fused stacked discriminator takes
@@ -371,3 +380,63 @@ class StackDiscNet(_FusedDiscNet):
         shape_logits = self.conv5(m.view(B, 1, N))  # B x S x N
         out = torch.logsumexp(shape_logits.transpose(2, 1), dim=2, keepdim=True)
         return shape_logits, out / (out + 1.0)
+
+
+class BaseDiscNet(nn.Module):
+    """models/discriminator.py:82-98, the dual discriminator's shared trunk.
+    forward(x: B x input_dim x N) -> B x output_dim x N.  conv4 is registered,
+    as in the reference, and never used: it receives no gradient."""
+
+    def __init__(self, input_pts, input_dim, output_dim):
+        super().__init__()
+        self.input_pts = input_pts
+        self.input_dim, self.output_dim = int(input_dim), int(output_dim)
+        self.conv1 = nn.Conv1d(input_dim, 64, 1)
+        self.conv2 = nn.Conv1d(64, 64, 1)
+        self.conv3 = nn.Conv1d(64, output_dim, 1)
+        self.conv4 = nn.Conv1d(output_dim, output_dim, 1)
+        self.leaky_relu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+
+    def forward(self, x):
+        for conv in (self.conv1, self.conv2, self.conv3):
+            x = self.leaky_relu(conv(x))
+        return x
+
+
+class ShapeDiscNet(nn.Module):
+    """models/discriminator.py:100-117.  forward(x: B x shared_output_dim x N)
+    -> B x num_shapes (the max runs over the points of each cloud)."""
+
+    def __init__(self, shared_output_dim, num_shapes):
+        super().__init__()
+        self.interm_dim = 512
+        self.shared_output_dim, self.num_shapes = int(shared_output_dim), int(num_shapes)
+        self.conv = nn.Conv1d(shared_output_dim, self.interm_dim, 1)
+        self.fc1 = nn.Linear(self.interm_dim, 64)
+        self.fc2 = nn.Linear(64, num_shapes)
+        self.leaky_relu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+
+    def forward(self, x):
+        x = self.leaky_relu(self.conv(x))
+        x = torch.max(x, 2, keepdim=False)[0].view(-1, self.interm_dim)
+        return self.fc2(self.leaky_relu(self.fc1(x)))
+
+
+class PointDiscNet(nn.Module):
+    """models/discriminator.py:119-137.  forward(x: B x shared_output_dim x N)
+    -> B*N/input_pts x input_pts: per point the max over the 128 channels."""
+
+    def __init__(self, shared_output_dim, input_pts):
+        super().__init__()
+        self.input_pts = input_pts
+        self.shared_output_dim = int(shared_output_dim)
+        self.conv1 = nn.Conv1d(shared_output_dim, 256, 1)
+        self.conv2 = nn.Conv1d(256, 128, 1)
+        self.conv3 = nn.Conv1d(128, 128, 1)
+        self.leaky_relu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+
+    def forward(self, x):
+        for conv in (self.conv1, self.conv2, self.conv3):
+            x = self.leaky_relu(conv(x))
+        x = torch.max(x.transpose(2, 1), 2, keepdim=True)[0]
+        return x.view(-1, self.input_pts)

@@ -6,7 +6,8 @@ import sys
 import torch
 from torch.nn import init
 
-from .discriminator import DeepConvDiscNet, PointwiseDiscNet, StackDiscNet
+from .discriminator import (BaseDiscNet, DeepConvDiscNet, PointDiscNet, PointwiseDiscNet,
+                            ShapeDiscNet, StackDiscNet)
 from .pointnet import PointNetCls
 
 
@@ -56,8 +57,9 @@ def init_weights(net, init_type, init_gain=1.0, verbose=True):
 def load_models(mode, device, args):
     """utils/model_utils.py:60-140 for the hot path's modes 'cls' and 'disc', the
     segmentation row's 'seg', its per-point discriminator 'disc_seg', the
-    stacked shape discriminator 'disc_stack' and the regularised generator
-    'seg_regu'.  The dual discriminator is outside this build's scope."""
+    stacked shape discriminator 'disc_stack', the regularised generator
+    'seg_regu' and the dual discriminator 'disc_dual' (:116-133), which returns
+    the tuple (shared, shape, point) of BaseDiscNet, ShapeDiscNet, PointDiscNet."""
     if mode == "cls":
         model = PointNetCls(k=40, feature_transform=False).to(device)
         try:
@@ -95,8 +97,11 @@ def load_models(mode, device, args):
             print("Loading pretrained cls model ...")
             model.load_state_dict(torch.load(args.checkpoint, map_location=device,
                                              weights_only=True))
-    elif mode == "disc_dual":
-        raise NotImplementedError(f"mode {mode!r} is outside the adversarial cls hot path")
+    elif mode == "disc_dual":  # :116-133, run_training_seg_dual's three nets
+        shared = BaseDiscNet(input_pts=args.input_pts, input_dim=args.disc_indim, output_dim=256)
+        shape = ShapeDiscNet(shared_output_dim=256, num_shapes=16)
+        point = PointDiscNet(shared_output_dim=256, input_pts=args.input_pts)
+        return tuple(init_net(m, device, init_type=args.init_disc) for m in (shared, shape, point))
     else:
         raise ValueError("Invalid mode {}!".format(mode))
     return model

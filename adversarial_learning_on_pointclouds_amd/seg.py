@@ -46,7 +46,8 @@ from .step import FusedStep
 
 __all__ = ["PointNetSeg", "PointNetSeg_regulization", "SegTrainStep", "SegAdvTrainStep",
            "SegStackTrainStep", "SegStackReguTrainStep", "seg_cross_entropy", "seg_forward",
-           "seg_backward", "segregu_forward", "segregu_backward"]
+           "seg_backward", "segregu_forward", "segregu_backward", "SegDualTrainStep",
+           "dualdisc_point", "dualdisc_shape", "sgd_"]
 
 _LOC = 960                       # x1..x5 widths 64 + 128 + 128 + 128 + 512
 PRECISIONS = ("fp32", "bf16x3")
@@ -1207,3 +1208,430 @@ class SegStackReguTrainStep(SegStackTrainStep):
                               ws=self._regu_ws)
             torch.add(self.loss_buf[6], self.loss_buf[7], out=self.loss_buf[8])
         segregu_backward(fw, d, None, out=self.grad_views, reg=reg)
+
+
+# ---------------------------------------------------------------------------
+# The dual discriminator of run_training_seg_dual (utils/trainer.py:2123-2382):
+# BaseDiscNet + PointDiscNet + ShapeDiscNet on the dense engine.  Every layer
+# is pcadv_gemm (six products, no activation) followed by pcadv_lrelu_fwd in
+# place; every data gradient pcadv_gemm (tb = 1) followed by pcadv_lrelu_bwd on
+# the activation below; every weight gradient pcadv_gemm_wgrad (csrc/
+# dualdisc.hip has the rest: the input transform, the point head's tail, SGD).
+# ---------------------------------------------------------------------------
+
+def _lrelu(E, y):
+    check(E.lib.pcadv_lrelu_fwd(_p(y), y.numel(), stream_ptr()), "pcadv_lrelu_fwd")
+
+
+def _lrelu_bwd(E, d, y, y_off=0):
+    check(E.lib.pcadv_lrelu_bwd(_p(d), _p(y, y_off), d.numel(), stream_ptr()), "pcadv_lrelu_bwd")
+
+
+def _dual_layer(E, x, w, b, rows):
+    """lrelu(x w^T + b) of the first `rows` rows of x; w a Conv1d weight [O][K](, 1)."""
+    O, K = w.shape[0], w.shape[1]
+    y = torch.empty(rows, O, device=x.device)
+    if rows:
+        E.gemm(x, K, w, K, y, O, rows, O, K, bias=b, precise=True)
+        _lrelu(E, y)
+    return y
+
+
+def _dual_dgrad(E, dz, w, rows, y_below, y_off=0):
+    """dz W of `rows` rows, times the LeakyReLU slope of the layer below's
+    output y_below (from element y_off on; None: the net's input, no slope)."""
+    O, K = w.shape[0], w.shape[1]
+    dx = torch.empty(rows, K, device=dz.device)
+    E.gemm(dz, O, w, K, dx, K, rows, K, O, tb=1, precise=True)
+    if y_below is not None:
+        _lrelu_bwd(E, dx, y_below, y_off)
+    return dx
+
+
+def _dual_wgrad(E, dz, x, rows, w, dw, db, accumulate):
+    O, K = w.shape[0], w.shape[1]
+    nb = E.lib.pcadv_gemm_wgrad_workspace_bytes(rows, O, K, 0)
+    ws = _ws(nb, dz.device)
+    check(E.lib.pcadv_gemm_wgrad(_p(dz), O, _p(x), K, rows, O, K, _p(dw), K, _p(db), None, 0,
+                                 int(accumulate), _p(ws), ws.numel(), stream_ptr()),
+          "pcadv_gemm_wgrad")
+
+
+def _dual_params(ps, n, name):
+    if len(ps) < n:
+        raise ValueError(f"{name}: expected at least {n} tensors (weights and biases)")
+    for t in ps[:n]:
+        _check_dev(t, name)
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: expected contiguous tensors")
+    return list(ps[:n])
+
+
+def dualdisc_point(logits, ncls, n0, n1, t0, t1, sp, pp, *, losses=None, soft0=None, soft1=None,
+                   soft_out=None, seed=0, step_count=None, lambda_adv=1.0, grads_s=None,
+                   grads_p=None, dlogits=None, max_workgroups=0):
+    """PointDiscNet(BaseDiscNet(.)) on the n0 + n1 point-major rows of `logits`
+    (row stride logits.stride(0); rows [0, n0) through transform t0, the rest
+    through t1), on the current stream.  sp: the trunk's conv1..conv3 weights and
+    biases (6 tensors, state_dict order), pp: the point head's.
+
+    Returns a dict: x0 (the transformed rows), acts (x0 and the six layers'
+    outputs), out (per row the max over the head's channels), argc (its
+    channel, the first on ties).  With `losses` (4 floats) also the BCE terms
+    and their derivatives as pcadv_pwdisc_forward defines them (dout_d,
+    dout_adv in the dict; labels soft0 / soft1 or device-drawn by (seed,
+    *step_count, row)); then grads_s / grads_p (six parameter-shaped tensors
+    each) receive the gradients of loss_D_point (overwritten), and rows
+    [n0, n0 + n1) of dlogits (point-major like logits) the gradient of
+    lambda_adv loss_adv through the frozen nets; its other rows are untouched."""
+    E = _engine()
+    dev = logits.device
+    R = n0 + n1
+    if logits.dim() != 2 or logits.shape[0] != R or logits.shape[1] < ncls \
+            or logits.stride(1) != 1 or R < 1:
+        raise ValueError(f"logits: expected point-major ({R}, >= {ncls}) rows, "
+                         f"got {tuple(logits.shape)} with strides {logits.stride()}")
+    _check_dev(logits, "logits")
+    sp, pp = _dual_params(sp, 6, "trunk parameters"), _dual_params(pp, 6, "point-head parameters")
+    if sp[0].shape[1] != ncls or pp[0].shape[1] != sp[4].shape[0] or pp[4].shape[0] % 4:
+        raise ValueError("dualdisc_point: the nets' widths do not chain from the logits' classes")
+    ld = max(logits.stride(0), ncls)
+    x0 = torch.empty(R, ncls, device=dev)
+    check(E.lib.pcadv_dual_input(_p(logits), ld, ncls, n0, n1, int(t0), int(t1), _p(x0),
+                                 stream_ptr()), "pcadv_dual_input")
+    W = [sp[0], sp[2], sp[4], pp[0], pp[2], pp[4]]
+    Bs = [sp[1], sp[3], sp[5], pp[1], pp[3], pp[5]]
+    acts = [x0]
+    for w, b in zip(W, Bs):
+        acts.append(_dual_layer(E, acts[-1], w, b, R))
+    y = acts[-1]
+    C = y.shape[1]
+    res = dict(x0=x0, acts=acts, out=torch.empty(R, device=dev),
+               argc=torch.empty(R, device=dev, dtype=torch.int32))
+    a = _lib.DualTailArgs()
+    a.y, a.C, a.n0, a.n1 = y.data_ptr(), C, n0, n1
+    a.out, a.argc = res["out"].data_ptr(), res["argc"].data_ptr()
+    a.max_workgroups = int(max_workgroups)
+    keep = []
+    if losses is not None:
+        if losses.numel() != 4 or losses.dtype != torch.float32 or not losses.is_contiguous():
+            raise ValueError("losses: expected 4 contiguous float32")
+        for t, n, nm in ((soft0, n0, "soft0"), (soft1, n1, "soft1"), (soft_out, R, "soft_out")):
+            if t is not None:
+                _check_dev(t, nm)
+                if t.numel() != n or not t.is_contiguous():
+                    raise ValueError(f"{nm}: expected {n} contiguous float32")
+        res["dout_d"] = torch.empty(R, device=dev)
+        res["dout_adv"] = torch.empty(max(n1, 1), device=dev)
+        dz_d = torch.empty(R, C, device=dev) if grads_s is not None else None
+        want_dx = dlogits is not None and n1 > 0
+        dz_adv = torch.empty(n1, C, device=dev) if want_dx else None
+        ws = _ws(E.lib.pcadv_dual_point_tail_workspace_bytes(R), dev)
+        keep += [dz_d, dz_adv, ws]
+        a.losses = losses.data_ptr()
+        a.soft0 = None if soft0 is None else soft0.data_ptr()
+        a.soft1 = None if soft1 is None else soft1.data_ptr()
+        a.soft_out = None if soft_out is None else soft_out.data_ptr()
+        a.rng_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        a.step_count = None if step_count is None else step_count.data_ptr()
+        a.dout_d, a.dout_adv = res["dout_d"].data_ptr(), res["dout_adv"].data_ptr()
+        a.lambda_adv = float(lambda_adv)
+        a.dz_d = None if dz_d is None else dz_d.data_ptr()
+        a.dz_adv = None if dz_adv is None else dz_adv.data_ptr()
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(E.lib.pcadv_dual_point_tail(ctypes.byref(a), stream_ptr()), "pcadv_dual_point_tail")
+    if losses is None:
+        return res
+    if grads_s is not None:
+        G = list(grads_s[:6]) + list(grads_p[:6])
+        for g, p in zip(G, sp + pp):
+            _check_dev(g, "D gradient")
+            if g.numel() != p.numel() or not g.is_contiguous():
+                raise ValueError("D gradients: expected parameter-shaped contiguous tensors")
+        dz = dz_d
+        for i in range(5, -1, -1):
+            _dual_wgrad(E, dz, acts[i], R, W[i], G[2 * i], G[2 * i + 1], False)
+            if i:
+                dz = _dual_dgrad(E, dz, W[i], R, acts[i])
+    if want_dx:
+        if dlogits.dim() != 2 or dlogits.shape[0] != R or dlogits.shape[1] < ncls \
+                or dlogits.stride(1) != 1 or dlogits.dtype != torch.float32 \
+                or dlogits.device.type != "cuda":
+            raise ValueError("dlogits: expected point-major float32 rows like logits")
+        dz = dz_adv
+        for i in range(5, -1, -1):
+            dz = _dual_dgrad(E, dz, W[i], n1, acts[i] if i else None, n0 * acts[i].shape[1])
+        ldd = max(dlogits.stride(0), ncls)
+        check(E.lib.pcadv_dual_input_bwd(_p(x0, n0 * ncls), _p(dz), ncls, n1, int(t1),
+                                         _p(dlogits, n0 * ldd), ldd, stream_ptr()),
+              "pcadv_dual_input_bwd")
+    return res
+
+
+def dualdisc_shape(x0, C, N, sp, hp, labels, scale, loss, grads_s, grads_h):
+    """ShapeDiscNet(BaseDiscNet(.)) and CrossEntropyLoss on C clouds of N points
+    whose transformed rows x0 (C N, ncls) are given, forward and backward, on
+    the current stream.  sp as in dualdisc_point; hp: the shape head's conv,
+    fc1, fc2 weights and biases; labels (C,) int64; loss: one float, the
+    unscaled mean cross entropy.  The gradients of scale x loss: grads_h (six
+    tensors) overwritten, grads_s (six tensors) ADDED to (the reference does not
+    clear the trunk's .grad between its two D terms).  Returns a dict: acts (x0
+    and the trunk's outputs), gmax / gidx (the conv's max over the points
+    before the LeakyReLU, which is increasing and so keeps the winner, and its
+    point, the first on ties), logits (C, num_shapes)."""
+    E = _engine()
+    dev = x0.device
+    M = C * N
+    sp, hp = _dual_params(sp, 6, "trunk parameters"), _dual_params(hp, 6, "shape-head parameters")
+    _check_dev(x0, "x0", shape=(M, sp[0].shape[1]))
+    _check_dev(labels, "labels", shape=(C,), dtype=torch.int64)
+    W = [sp[0], sp[2], sp[4]]
+    acts = [x0.contiguous()]
+    for i, w in enumerate(W):
+        acts.append(_dual_layer(E, acts[-1], w, sp[2 * i + 1], M))
+    h3 = acts[-1]
+    K, O = h3.shape[1], hp[0].shape[0]
+    if hp[0].shape[1] != K or K % 32 or K > 512:
+        raise ValueError(f"dualdisc_shape: trunk width {K} (a multiple of 32 up to 512) against "
+                         f"the head's {hp[0].shape[1]}")
+    gmax = torch.empty(C, O, device=dev)
+    gidx = torch.empty(C, O, device=dev, dtype=torch.int32)
+    ws = _ws(E.lib.pcadv_conv_max_x3_workspace_bytes(C, N, O), dev)
+    check(E.lib.pcadv_conv_max_x3(_p(h3), K, C, N, K, _p(hp[0]), _p(hp[1]), O, 0, _p(gmax),
+                                  _p(gidx), _p(ws), ws.numel(), stream_ptr()), "pcadv_conv_max_x3")
+    pooled = gmax.clone()
+    _lrelu(E, pooled)
+    f1 = ops.linear_fwd(pooled, hp[2], hp[3], ops.ACT_LRELU)
+    s = ops.linear_fwd(f1, hp[4], hp[5], ops.ACT_NONE)
+    S = s.shape[1]
+    ds = torch.empty_like(s)
+    cws = _ws(E.lib.pcadv_row_ce_workspace_bytes(C), dev)
+    check(E.lib.pcadv_row_ce(_p(s), S, _p(labels), C, S, float(scale), _p(loss), _p(ds), _p(cws),
+                             cws.numel(), stream_ptr()), "pcadv_row_ce")
+    df1, _, _ = ops.linear_bwd(ds, s, ops.ACT_NONE, None, 0.0, f1, hp[4], dw_out=grads_h[4],
+                               db_out=grads_h[5])
+    dpool, _, _ = ops.linear_bwd(df1, f1, ops.ACT_LRELU, None, 0.0, pooled, hp[2],
+                                 dw_out=grads_h[2], db_out=grads_h[3])
+    _lrelu_bwd(E, dpool, pooled)
+    # pcadv_conv_max_x3_bwd masks by [gmax > 0] (the ReLU before conv6's max); the
+    # LeakyReLU's slope is already in dpool, so every channel passes
+    ones = torch.ones(C, O, device=dev)
+    dh3 = torch.zeros(M, K, device=dev)
+    check(E.lib.pcadv_conv_max_x3_bwd(_p(dpool), _p(ones), _p(gidx), _p(h3), K, C, N, O, K,
+                                      _p(hp[0]), _p(grads_h[0]), _p(grads_h[1]), _p(dh3), K, 0,
+                                      stream_ptr()), "pcadv_conv_max_x3_bwd")
+    _lrelu_bwd(E, dh3, h3)
+    dz = dh3
+    for i in range(2, -1, -1):
+        _dual_wgrad(E, dz, acts[i], M, W[i], grads_s[2 * i], grads_s[2 * i + 1], True)
+        if i:
+            dz = _dual_dgrad(E, dz, W[i], M, acts[i])
+    return dict(acts=acts, gmax=gmax, gidx=gidx, pooled=pooled, logits=s, dh3=dh3)
+
+
+def sgd_(param, grad, lr, acc=None):
+    """pcadv_sgd on flat float32 tensors: param -= lr grad, or with acc (a
+    running gradient sum) acc += grad; param -= lr acc."""
+    n = param.numel()
+    for t, nm in ((param, "param"), (grad, "grad"), (acc, "acc")):
+        if t is None:
+            continue
+        _check_dev(t, nm)
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"sgd: {nm} has {t.numel()} elements, expected {n} contiguous")
+    check(_engine().lib.pcadv_sgd(_p(param), _p(grad), None if acc is None else _p(acc), n,
+                                  float(lr), stream_ptr()), "pcadv_sgd")
+
+
+def _plain_sgd_lr(opt, nets, what):
+    """The learning rate of a torch.optim.SGD the fused dual step can stand in
+    for: one param group over exactly `nets`' parameters, no momentum,
+    dampening, weight decay, nesterov or maximize."""
+    if type(opt) is not torch.optim.SGD or len(opt.param_groups) != 1:
+        raise ValueError(f"{what}: expected a torch.optim.SGD with one param group")
+    g = opt.param_groups[0]
+    if g.get("momentum", 0) or g.get("dampening", 0) or g.get("weight_decay", 0) \
+            or g.get("nesterov") or g.get("maximize"):
+        raise ValueError(f"{what}: plain SGD only (no momentum, dampening, weight decay, nesterov "
+                         "or maximize)")
+    want = {id(p) for net in nets for p in net.parameters()}
+    if {id(p) for p in g["params"]} != want or len(g["params"]) != len(want):
+        raise ValueError(f"{what}: its parameters are not exactly its head's and the trunk's")
+    return float(g["lr"])
+
+
+class SegDualTrainStep(_SegStep):
+    """One iteration of run_training_seg_dual (utils/trainer.py:2151-2286) with
+    PointNetSeg + BaseDiscNet / ShapeDiscNet / PointDiscNet, ImagePool(0), G's
+    Adam and the two plain SGDs that both own the trunk, as native launches on
+    one stream, capturable into one HIP graph (no parallel branches):
+
+      weight-plane split; seg_forward on the 2B clouds [GT; no-GT]; pcadv_row_ce
+      on the GT rows; the point phase (dualdisc_point) on [softmax(GT);
+      log_softmax(no-GT)]: loss_adv, loss_D_point, the trunk's and the point
+      head's gradients of loss_D_point and the no-GT rows of dlogits from
+      lambda_adv loss_adv; seg_backward; G's Adam; optimizer_D_point.step() as
+      two pcadv_sgd launches; the shape phase (dualdisc_shape) on the GT rows
+      through the UPDATED trunk, its trunk gradients added to the point phase's;
+      optimizer_D_shape.step() as two more.
+
+    The reference runs D three times in the point phase (frozen on the no-GT
+    rows for G's term, then on each detached half for its own): D has no batch
+    statistics or dropout and G's Adam does not touch it, so one forward serves
+    all three.  G's Adam is placed after G's backward; the reference steps it
+    before D's terms, which read detached predictions: the same values.
+
+    The reference never clears PointDiscNet's gradients (optimizer_D_point.
+    zero_grad() is not called in its loop), so its SGD steps by the running sum
+    A_P of every iteration's gradient.  That sum lives in the point head's flat
+    .grad buffer (pcadv_sgd's accumulator form), so an eager iteration continues
+    it; the trunk's .grad holds g_S^P + g_S^H and the shape head's g_H after a
+    step, conv4's (never used by forward) zeros.  The three nets' parameters and
+    gradients are flat buffers handed to the modules as views.  D always runs in
+    f32; `precision` is the generator's.  `losses` is [loss_seg, loss_adv,
+    loss_D_point, loss_D_shape] (loss_D_shape unscaled)."""
+
+    def __init__(self, model, sharedDisc, shapeDisc, pointDisc, optimizer=None,
+                 optimizer_D_shape=None, optimizer_D_point=None, lambda_seg=1.0, lambda_adv=0.01,
+                 lambda_disc_shape=1.0, lr=1e-4, lr_D_shape=1e-4, lr_D_point=1e-4,
+                 betas=(0.9, 0.999), eps=1e-8, device="cuda", precision=None, seed=0,
+                 keep_activations=False):
+        from .discriminator import BaseDiscNet, PointDiscNet, ShapeDiscNet
+        if not (isinstance(model, PointNetSeg) and isinstance(sharedDisc, BaseDiscNet)
+                and isinstance(shapeDisc, ShapeDiscNet) and isinstance(pointDisc, PointDiscNet)):
+            raise TypeError("SegDualTrainStep: expected a PointNetSeg, a BaseDiscNet, a "
+                            "ShapeDiscNet and a PointDiscNet")
+        if sharedDisc.input_dim != model.output_dim:
+            raise ValueError(f"sharedDisc takes {sharedDisc.input_dim} channels, the generator "
+                             f"predicts {model.output_dim} classes")
+        if not (sharedDisc.output_dim == shapeDisc.shared_output_dim
+                == pointDisc.shared_output_dim == 256) or shapeDisc.interm_dim != 512:
+            raise ValueError("SegDualTrainStep: a 256-wide trunk and a 512-wide shape conv")
+        if shapeDisc.num_shapes < 16:
+            raise ValueError(f"shapeDisc has {shapeDisc.num_shapes} shape classes, cls is 16 wide")
+        self._d_opts = (optimizer_D_shape, optimizer_D_point)
+        self._d_nets = (sharedDisc, shapeDisc, pointDisc)
+        self.lr_D_shape, self.lr_D_point = float(lr_D_shape), float(lr_D_point)
+        super().__init__(model, (optimizer,), [(lr, betas, eps)], device, precision,
+                         keep_activations)
+        dev = self.device
+        self.sharedDisc, self.shapeDisc, self.pointDisc = sharedDisc, shapeDisc, pointDisc
+        # FlatAdam without an optimizer: flat parameters and gradients as views
+        self.S, self.H, self.P = (FlatAdam(m, None, dev) for m in self._d_nets)
+        # this iteration's point-head gradient; P.grad is the running sum A_P
+        self.gp = torch.zeros(self.P.numel, device=dev)
+        self.gp_views = list(self.P.views(self.gp).values())
+        self.lambda_seg, self.lambda_adv = float(lambda_seg), float(lambda_adv)
+        self.lambda_disc_shape, self.seed = float(lambda_disc_shape), int(seed)
+        # [loss_seg, loss_adv, loss_D_point, its GT part, its no-GT part, loss_D_shape]
+        self.loss_buf = torch.zeros(6, device=dev)
+        self._loss_idx = torch.tensor([0, 1, 2, 5], device=dev)
+        self.d_out = self.act = None
+
+    def sync_hyper(self):
+        super().sync_hyper()
+        shared, shape, point = self._d_nets
+        if self._d_opts[0] is not None:
+            self.lr_D_shape = _plain_sgd_lr(self._d_opts[0], (shape, shared), "optimizer_D_shape")
+        if self._d_opts[1] is not None:
+            self.lr_D_point = _plain_sgd_lr(self._d_opts[1], (point, shared), "optimizer_D_point")
+
+    def graph_state(self):
+        """The base's list and what else a warm-up changes: the three D nets'
+        parameters and the running sum A_P."""
+        return super().graph_state() + [self.S.param, self.H.param, self.P.param, self.P.grad]
+
+    def after_eager(self):
+        """The base's hand-over for G; the D nets' .grad go back to their flat
+        views (a fresh tensor's values copied in, None as zeros).  The point
+        head's were accumulated in place by the eager iterations, so A_P
+        carries on."""
+        super().after_eager()
+        for f in (self.S, self.H, self.P):
+            for p, gv in zip(f.params, f.grad_views):
+                if p.grad is None:
+                    gv.zero_()
+                elif p.grad.data_ptr() != gv.data_ptr():
+                    gv.copy_(p.grad)
+                p.grad = gv
+
+    def __call__(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
+                 apply_adam=True):
+        self._run(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, apply_adam)
+        return self.losses
+
+    def _run(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, apply_adam):
+        """The step's launches and nothing else: what capture_on captures.
+        apply_adam False: the gradients only (no Adam, no SGD; the shape phase
+        then sees the trunk as it was, and A_P still takes this gradient)."""
+        B, N, _ = pts_gt.shape
+        _check_dev(pts_gt, "pts_gt")
+        _check_dev(pts_nogt, "pts_nogt", shape=(B, N, 3))
+        if seg.shape != (B, N) or seg.dtype != torch.int64 or not seg.is_contiguous():
+            raise ValueError("seg: expected contiguous int64 (B, N)")
+        if (B * N) % int(self.pointDisc.input_pts):
+            raise ValueError(f"{B} x {N} points do not fill rows of pointDisc.input_pts = "
+                             f"{self.pointDisc.input_pts}")
+        M = B * N
+        wpl = None
+        if _PLANES:
+            _engine().split(self.param, self.wph, self.wpl)
+            wpl = self.wplanes
+        pts = torch.cat([pts_gt, pts_nogt])
+        cls_gt = cls_gt.float().reshape(B, 1, 16)
+        cls = torch.cat([cls_gt, cls_nogt.float().reshape(B, 1, 16)])
+        fw = seg_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
+        ncls = fw["dims"][2]
+        logits = fw["logits"]
+        d = torch.empty(2 * M, ncls, device=self.device)
+        ws = _ws(self.lib.pcadv_row_ce_workspace_bytes(M), self.device)
+        check(self.lib.pcadv_row_ce(_p(logits), ncls, _p(seg), M, ncls, self.lambda_seg,
+                                    _p(self.loss_buf), _p(d), _p(ws), ws.numel(), stream_ptr()),
+              "pcadv_row_ce")
+        S, H, P = self.S, self.H, self.P
+        act = dualdisc_point(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, S.params[:6],
+                             P.params, losses=self.loss_buf[1:5],
+                             soft0=None if soft_gt is None else soft_gt.reshape(M),
+                             soft1=None if soft_nogt is None else soft_nogt.reshape(M),
+                             seed=self.seed, step_count=self.step_count,
+                             lambda_adv=self.lambda_adv, grads_s=S.grad_views[:6],
+                             grads_p=self.gp_views, dlogits=d)
+        seg_backward(fw, d, None, out=self.grad_views)
+        if apply_adam:
+            self._adam(0, self.lr, self.betas, self.eps)
+            # optimizer_D_point.step(): the head by its running sum, the trunk by g_S^P
+            sgd_(P.param, self.gp, self.lr_D_point, acc=P.grad)
+            sgd_(S.param, S.grad, self.lr_D_point)
+        else:
+            P.grad += self.gp
+        labels = torch.argmax(cls_gt.reshape(B, 16), dim=1)
+        x0_gt = act["x0"][:M]
+        sh = dualdisc_shape(x0_gt, B, N, S.params[:6], H.params, labels, self.lambda_disc_shape,
+                            self.loss_buf[5:6], S.grad_views[:6], H.grad_views)
+        if apply_adam:
+            # optimizer_D_shape.step(): the trunk by g_S^P + g_S^H
+            sgd_(H.param, H.grad, self.lr_D_shape)
+            sgd_(S.param, S.grad, self.lr_D_shape)
+        if self.keep_activations:
+            self.fw, self.d_out, self.act = fw, act["out"], dict(point=act, shape=sh)
+
+    def adam(self):
+        raise NotImplementedError("SegDualTrainStep: the updates are interleaved with the two D "
+                                  "phases (the shape phase reads the updated trunk); call the step")
+
+    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None):
+        """One HIP graph of a step reading the given resident buffers: a single
+        stream, no parallel branches (state, A_P included, is restored to what
+        it was before the warm-up)."""
+        def body():
+            self._run(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt, True)
+        return self._capture(body, body)
+
+    @property
+    def losses(self):
+        """[loss_seg, loss_adv, loss_D_point, loss_D_shape], the order of the
+        reference's log line (a gather by a resident index: a new tensor)."""
+        return self.loss_buf.index_select(0, self._loss_idx)
+
+    def logged(self, with_semi=False):
+        return self.losses.tolist()

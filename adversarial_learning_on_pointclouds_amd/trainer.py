@@ -1514,3 +1514,204 @@ def run_training_seg_stack_regulization(trainloader_gt, trainloader_nogt, trainl
                          seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
                          train_logger, test_logger, writer, args, shape_criterion=shape_criterion,
                          regu_loss=regu_loss)
+
+
+def _seg_dual_fusable(model, sharedDisc, shapeDisc, pointDisc, optimizer, optimizer_D_shape,
+                      optimizer_D_point, gan_point_loss, gan_shape_loss, seg_loss, pool_gt,
+                      pool_nogt, args):
+    """The configuration SegDualTrainStep implements: PointNetSeg, the three
+    dual-discriminator nets (256-wide trunk, 512-wide shape conv, at least 16
+    shape classes), a plain Adam for G, two plain one-group SGDs over exactly
+    shape + shared and point + shared, BCEWithLogitsLoss and two plain
+    CrossEntropyLoss, both pools of size 0, the HIP device."""
+    from .discriminator import BaseDiscNet, PointDiscNet, ShapeDiscNet
+    from .seg import PointNetSeg, _plain_sgd_lr
+    if not (isinstance(model, PointNetSeg) and isinstance(sharedDisc, BaseDiscNet)
+            and isinstance(shapeDisc, ShapeDiscNet) and isinstance(pointDisc, PointDiscNet)):
+        return False
+    if sharedDisc.input_dim != model.output_dim or str(args.device).split(":")[0] != "cuda":
+        return False
+    if not (sharedDisc.output_dim == shapeDisc.shared_output_dim == pointDisc.shared_output_dim
+            == 256) or shapeDisc.interm_dim != 512 or shapeDisc.num_shapes < 16:
+        return False
+    if type(optimizer) is not torch.optim.Adam or len(optimizer.param_groups) != 1:
+        return False
+    g = optimizer.param_groups[0]
+    if g.get("weight_decay", 0) or g.get("amsgrad") or g.get("maximize"):
+        return False
+    try:
+        _plain_sgd_lr(optimizer_D_shape, (shapeDisc, sharedDisc), "optimizer_D_shape")
+        _plain_sgd_lr(optimizer_D_point, (pointDisc, sharedDisc), "optimizer_D_point")
+    except ValueError:
+        return False
+    if type(gan_point_loss) is not torch.nn.BCEWithLogitsLoss or gan_point_loss.weight is not None \
+            or gan_point_loss.pos_weight is not None or gan_point_loss.reduction != "mean":
+        return False
+    if not _plain_ce(gan_shape_loss) or not _plain_ce(seg_loss):
+        return False
+    return getattr(pool_gt, "pool_size", 1) == 0 and getattr(pool_nogt, "pool_size", 1) == 0
+
+
+def _seg_dual_d_part(sharedDisc, shapeDisc, pointDisc, optimizer_D_shape, optimizer_D_point,
+                     gan_point_loss, gan_shape_loss, pool_gt, pool_nogt, pred_gt_softmax,
+                     pred_nogt_softmax, cls, args, soft=None):
+    """utils/trainer.py:2236-2286, the two D terms of an iteration on detached
+    predictions: the point term and optimizer_D_point.step(), then the shape
+    term through the updated trunk and optimizer_D_shape.step().  No gradient is
+    cleared here (the iteration's top clears the trunk's and the shape head's;
+    nothing ever clears the point head's).  soft: (soft_gt, soft_nogt) in place
+    of make_D_label's draws.  Returns (loss_D_point, loss_D_shape) as floats."""
+    loss_D_point_value, terms = 0.0, []
+    for k, (pool, x, value) in enumerate(((pool_gt, pred_gt_softmax, 1),
+                                          (pool_nogt, pred_nogt_softmax, 0))):
+        D_point = pointDisc(sharedDisc(pool.query(x.detach())))
+        label = make_D_label(input=D_point, value=value, device=args.device, random=True) \
+            if soft is None else soft[k].reshape(D_point.shape).to(D_point)
+        terms.append(0.5 * gan_point_loss(D_point, label))
+        loss_D_point_value += terms[-1].item()
+    (terms[0] + terms[1]).backward()
+    optimizer_D_point.step()
+    D_shape = shapeDisc(sharedDisc(pred_gt_softmax))
+    cls_gt = cls.argmax(dim=2).squeeze(1)
+    loss_D_shape = gan_shape_loss(D_shape, cls_gt.long())
+    (args.lambda_disc_shape * loss_D_shape).backward()
+    optimizer_D_shape.step()
+    return loss_D_point_value, loss_D_shape.item()
+
+
+def _seg_dual_body(model, sharedDisc, shapeDisc, pointDisc, optimizer, optimizer_D_shape,
+                   optimizer_D_point, gan_point_loss, gan_shape_loss, seg_loss, pool_gt, pool_nogt,
+                   pts, cls, seg, pts_nogt, cls_nogt, args, soft=None):
+    """utils/trainer.py:2165-2286 through autograd over the same modules, the
+    reference's gradient clearing included: optimizer and optimizer_D_shape are
+    cleared, optimizer_D_point never is, so the point head's gradients
+    accumulate over the iterations and its SGD steps by their running sum.
+    Returns [loss_seg, loss_adv, loss_D_point, loss_D_shape]."""
+    nets = (sharedDisc, shapeDisc, pointDisc)
+    optimizer.zero_grad()
+    optimizer_D_shape.zero_grad()
+    for net in nets:  # train G
+        for param in net.parameters():
+            param.requires_grad = False
+    pred, _ = model(pts, cls)
+    l_seg = seg_loss(pred, seg)
+    pred_gt_softmax = F.softmax(pred, dim=1)
+    pred_nogt, _ = model(pts_nogt, cls_nogt)
+    pred_nogt_softmax = F.log_softmax(pred_nogt, dim=1)
+    D_point = pointDisc(sharedDisc(pred_nogt_softmax))
+    loss_adv = gan_point_loss(D_point, make_D_label(input=D_point, value=1, device=args.device,
+                                                    random=False))
+    (args.lambda_seg * l_seg + args.lambda_adv * loss_adv).backward()
+    optimizer.step()
+    for net in nets:  # train D
+        for param in net.parameters():
+            param.requires_grad = True
+    d_point, d_shape = _seg_dual_d_part(
+        sharedDisc, shapeDisc, pointDisc, optimizer_D_shape, optimizer_D_point, gan_point_loss,
+        gan_shape_loss, pool_gt, pool_nogt, pred_gt_softmax.detach(), pred_nogt_softmax.detach(),
+        cls, args, soft=soft)
+    return [l_seg.item(), loss_adv.item(), d_point, d_shape]
+
+
+def run_training_seg_dual(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                          targetloader_nogt_iter, testloader, testdataset, model, sharedDisc,
+                          shapeDisc, pointDisc, gan_point_loss, gan_shape_loss, seg_loss, optimizer,
+                          optimizer_D_shape, optimizer_D_point, history_pool_gt, history_pool_nogt,
+                          train_logger, test_logger, writer, args):
+    """utils/trainer.py:2123-2382: adversarial segmentation with the dual
+    discriminator (a shared trunk, a per-point head trained by BCE-with-logits
+    and a shape head trained by cross entropy, two SGDs that both own the
+    trunk).  The log line, the tensorboard tags (Loss/train_seg | train_adv |
+    disc_point | disc_shape) and the checkpoints are the reference's:
+    model_train_epoch_{}.pth and sharedDisc_ / pointDisc_ / shapeDisc_train_
+    epoch_{}.pth, and by best IoU model_train_best_{cat,all}_iou.pth with the
+    three D files of the same stem WITHOUT the .pth suffix.
+
+    In the configuration of _seg_dual_fusable every iteration whose two batches
+    have the same shape and fill rows of pointDisc.input_pts is one
+    SegDualTrainStep; anything else, and a ragged last batch, runs
+    _seg_dual_body.  Returns (max_seg_accu, max_test_cat_iou, max_test_all_iou)."""
+    from .seg import SegDualTrainStep
+    max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
+    max_train_epoch = max_train_cat_epoch = max_train_all_epoch = 0
+    nets = (("sharedDisc", sharedDisc), ("pointDisc", pointDisc), ("shapeDisc", shapeDisc))
+    fusable = _seg_dual_fusable(model, sharedDisc, shapeDisc, pointDisc, optimizer,
+                                optimizer_D_shape, optimizer_D_point, gan_point_loss,
+                                gan_shape_loss, seg_loss, history_pool_gt, history_pool_nogt, args)
+    step, eager_since = None, False
+    tb = getattr(args, "tensorboard", False) and writer is not None
+    line = ('iter = {0:8d}/{1:8d} loss_seg = {2:.3f} loss_adv = {3:.3f} '
+            'loss D_point = {4:.3f} loss_D_shape = {5:.3f}')
+
+    def save(tag, d_suffix):
+        if step is not None:
+            step.sync_optimizer_state()
+        torch.save(model.state_dict(), os.path.join(args.exp_dir, "model_train_{}.pth".format(tag)))
+        for name, net in nets:
+            torch.save(net.state_dict(),
+                       os.path.join(args.exp_dir, "{}_train_{}{}".format(name, tag, d_suffix)))
+
+    for i_iter in range(args.total_iterations):
+        model.train()
+        for _, net in nets:
+            net.train()
+        batch, trainloader_gt_iter = _next(trainloader_gt, trainloader_gt_iter)
+        pts, cls, seg = batch
+        pts, cls, seg = pts.float().to(args.device), cls.float().to(args.device), \
+            seg.long().to(args.device)
+        batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
+        pts_nogt, cls_nogt = batch
+        pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
+        if fusable and pts.shape == pts_nogt.shape \
+                and (pts.shape[0] * pts.shape[1]) % int(pointDisc.input_pts) == 0:
+            if step is None:
+                step = SegDualTrainStep(
+                    model, sharedDisc, shapeDisc, pointDisc, optimizer=optimizer,
+                    optimizer_D_shape=optimizer_D_shape, optimizer_D_point=optimizer_D_point,
+                    lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
+                    lambda_disc_shape=args.lambda_disc_shape, device=args.device,
+                    seed=int(getattr(args, "seed", 0) or 0))
+            elif eager_since:
+                step.after_eager()
+            eager_since = False
+            step.sync_hyper()
+            step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
+                 cls_nogt.contiguous())
+            vals = step.logged()
+        else:
+            if step is not None:
+                step.sync_optimizer_state()
+            eager_since = True
+            vals = _seg_dual_body(model, sharedDisc, shapeDisc, pointDisc, optimizer,
+                                  optimizer_D_shape, optimizer_D_point, gan_point_loss,
+                                  gan_shape_loss, seg_loss, history_pool_gt, history_pool_nogt,
+                                  pts, cls, seg, pts_nogt, cls_nogt, args)
+        train_logger.info(line.format(i_iter, args.total_iterations, *vals))
+        if tb:
+            for tag, v in zip(('Loss/train_seg', 'Loss/train_adv', 'Loss/disc_point',
+                               'Loss/disc_shape'), vals):
+                writer.add_scalar(tag, v, i_iter)
+        if i_iter % args.iter_test_epoch == 0:
+            ep = i_iter // args.iter_test_epoch
+            train_logger.info("======= Testing on Epoch {} =======".format(ep))
+            save("epoch_{}".format(ep), ".pth")
+            accu, _, cat_iou, all_iou = run_testing_seg(
+                dataloader=testloader, dataset=testdataset, model=model, criterion=seg_loss,
+                logger=test_logger, test_iter=i_iter, writer=writer, args=args)
+            if max_seg_accu < accu:
+                max_seg_accu, max_train_epoch = accu, ep
+            if max_test_cat_iou < cat_iou:
+                max_test_cat_iou, max_train_cat_epoch = cat_iou, ep
+                save("best_cat_iou", "")
+            if max_test_all_iou < all_iou:
+                max_test_all_iou, max_train_all_epoch = all_iou, ep
+                save("best_all_iou", "")
+    if step is not None:
+        step.sync_optimizer_state()
+    train_logger.info("=========================")
+    train_logger.info("Max accuracy: {:.4f}, at epoch: {}".format(max_seg_accu, max_train_epoch))
+    train_logger.info("Max cat mIoU: {:.4f}, at epoch: {}".format(max_test_cat_iou, max_train_cat_epoch))
+    train_logger.info("Max all mIoU: {:.4f}, at epoch: {}".format(max_test_all_iou, max_train_all_epoch))
+    if tb:
+        writer.close()
+    return max_seg_accu, max_test_cat_iou, max_test_all_iou

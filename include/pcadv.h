@@ -922,6 +922,73 @@ int pcadv_cloud_xform_bwd(const float* dy, int64_t lddy, const float* x, int64_t
 int pcadv_tnet_mse_reg(const float* T, int C, int B0, int k, float scale, float* loss, float* dT,
                        float* workspace, hipStream_t stream);
 
+/* ---- The dual discriminator of run_training_seg_dual ------------------------
+ * (BaseDiscNet / PointDiscNet / ShapeDiscNet, models/discriminator.py:82-137;
+ * utils/trainer.py:2123-2382.)  Additive to ABI 11.  The nets' wide layers run
+ * on pcadv_gemm (precise = 1, no activation) and pcadv_gemm_wgrad, the shape
+ * head on pcadv_conv_max_x3 (relu = 0: LeakyReLU is increasing, so it commutes
+ * with the max and keeps the arg-max) and pcadv_linear_*; these entries are
+ * what the engine lacks.  Every sum runs in a fixed order (no atomics).
+ *
+ * pcadv_dual_input: x0[r][0..ncls) (dense, [n0 + n1][ncls]) = transform t0 of
+ * logits row r < n0, t1 of the other rows (PCADV_PWD_*; row stride ld,
+ * 2 <= ncls <= 64).  pcadv_dual_input_bwd: its backward on n rows of one
+ * transform t: from x0 (the transform's OUTPUT rows) and dx0 (both dense
+ * [n][ncls]) into dlogits (row stride ldd; columns >= ncls are not written). */
+int pcadv_dual_input(const float* logits, int64_t ld, int ncls, int64_t n0, int64_t n1, int t0,
+                     int t1, float* x0, hipStream_t stream);
+int pcadv_dual_input_bwd(const float* x0, const float* dx0, int ncls, int64_t n, int t,
+                         float* dlogits, int64_t ldd, hipStream_t stream);
+
+/* LeakyReLU(0.2) in place over n floats, and its derivative applied to a data
+ * gradient: d[i] *= (y[i] > 0 ? 1 : 0.2), y the activation's OUTPUT (slope 0.2
+ * at exactly 0, as the backward of torch's in-place LeakyReLU). */
+int pcadv_lrelu_fwd(float* y, int64_t n, hipStream_t stream);
+int pcadv_lrelu_bwd(float* d, const float* y, int64_t n, hipStream_t stream);
+
+/* PointDiscNet's tail on y [n0 + n1][C] (its last layer's output after the
+ * LeakyReLU; C % 4 == 0, 16-B aligned): out[row] = max over the C channels,
+ * argc[row] its channel (the first on ties).  With losses != NULL (4 floats)
+ * also the three BCE-with-logits terms exactly as pcadv_pwdisc_forward defines
+ * them (losses[0] = loss_adv, [1] = loss_D_point = [2] + [3]), the labels
+ * soft0 / soft1 or drawn with the same Philox keys (rng_seed, *step_count,
+ * row), dout_d [n0 + n1], dout_adv [n1] (optional), and the top gradients of
+ * the backward chains, one-hot at argc times the winner's LeakyReLU slope:
+ *   dz_d   [n0 + n1][C] (optional) = dout_d[row] slope,
+ *   dz_adv [n1][C]      (optional) = lambda_adv dout_adv[j] slope.
+ * max_workgroups: 0, or a cap on the grid (tests).  The workspace needs no
+ * zeroing. */
+typedef struct pcadv_dual_tail_args {
+  const float* y;
+  int C;
+  int64_t n0, n1;
+  float* out;
+  int32_t* argc;
+  float* losses;
+  const float* soft0;
+  const float* soft1;
+  float* soft_out;
+  uint64_t rng_seed;
+  const int32_t* step_count;
+  float* dout_d;
+  float* dout_adv;
+  float lambda_adv;
+  float* dz_d;
+  float* dz_adv;
+  int max_workgroups;
+  void* workspace;
+  size_t workspace_bytes;
+} pcadv_dual_tail_args;
+size_t pcadv_dual_point_tail_workspace_bytes(int64_t rows);
+int pcadv_dual_point_tail(const pcadv_dual_tail_args* args, hipStream_t stream);
+
+/* Plain SGD over a flat range (torch.optim.SGD without momentum, dampening or
+ * weight decay): p[i] -= lr g[i]; with acc != NULL first acc[i] += g[i] and the
+ * update takes acc[i] (a .grad that is never cleared: PointDiscNet's in
+ * run_training_seg_dual).  Any n and alignment (16-B stores where p, g and acc
+ * are 16-B aligned); product and difference rounded separately. */
+int pcadv_sgd(float* p, const float* g, float* acc, int64_t n, float lr, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

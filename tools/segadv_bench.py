@@ -31,6 +31,13 @@ scaled so the feature transform starts near the identity) against the stacked
 step of the same run (the conv / fc weights equal, the same 32 clouds and the
 same StackDiscNet weights), alternated the same way, into
 profiles/segregu_bench.json.
+
+--dual times run_training_seg_dual's step (SegDualTrainStep with BaseDiscNet /
+ShapeDiscNet / PointDiscNet, G's Adam and the two SGDs) as a replayed graph
+against trainer._seg_dual_body on equal modules (the reference's iteration
+through autograd and torch's own kernels, eager: it reads its losses on the
+host as the reference does), with the pointwise adversarial step for scale,
+alternated the same way, into profiles/segdual_bench.json.
 """
 import argparse
 import json
@@ -183,6 +190,77 @@ def _stack(a):
                       "round_spread_us": out["round_spread_us"], "d_alone": out["d_alone"]}))
 
 
+def _dual(a):
+    """--dual: SegDualTrainStep (graph) against _seg_dual_body (eager autograd)
+    and SegAdvTrainStep (graph)."""
+    import copy
+    import adversarial_learning_on_pointclouds_amd as pc
+    from adversarial_learning_on_pointclouds_amd import trainer
+    from adversarial_learning_on_pointclouds_amd.image_pool import ImagePool
+    B, N = 16, 2048
+    rng = np.random.default_rng(0)
+    torch.manual_seed(0)
+    pts, cls, seg = _inputs(rng, 2 * B, N)
+    halves = (pts[:B].contiguous(), cls[:B].contiguous(), seg[:B].contiguous(),
+              pts[B:].contiguous(), cls[B:].contiguous())
+    lrs = dict(lr=1e-4, lr_D_shape=1e-4, lr_D_point=1e-4)
+
+    def nets():
+        return (pc.BaseDiscNet(N, 50, 256).cuda(), pc.ShapeDiscNet(256, 16).cuda(),
+                pc.PointDiscNet(256, N).cuda())
+    g_dual, d_dual = pc.PointNetSeg(50).cuda(), nets()
+    g_body, d_body = copy.deepcopy(g_dual), copy.deepcopy(d_dual)
+    g_adv = copy.deepcopy(g_dual)
+    dual = pc.SegDualTrainStep(g_dual, *d_dual, lambda_adv=0.01, lambda_disc_shape=1.0, seed=5,
+                               **lrs)
+    adv = pc.SegAdvTrainStep(g_adv, pc.PointwiseDiscNet(N, 50).cuda(), lr=1e-4, lr_D=1e-4,
+                             lambda_adv=0.01, seed=5)
+    shared, shape, point = d_body
+    opts = (torch.optim.Adam(g_body.parameters(), lr=1e-4),
+            torch.optim.SGD(list(shape.parameters()) + list(shared.parameters()), lr=1e-4),
+            torch.optim.SGD(list(point.parameters()) + list(shared.parameters()), lr=1e-4))
+    crit = (torch.nn.BCEWithLogitsLoss(), torch.nn.CrossEntropyLoss(), torch.nn.CrossEntropyLoss())
+    pools = (ImagePool(0), ImagePool(0))
+    bargs = argparse.Namespace(device="cuda", lambda_seg=1.0, lambda_adv=0.01,
+                               lambda_disc_shape=1.0)
+    last = {}
+
+    def body():
+        last["v"] = trainer._seg_dual_body(g_body, shared, shape, point, *opts, *crit, *pools,
+                                           *halves, bargs)
+
+    class Eager:
+        def replay(self):
+            body()
+    graphs = {"dual": dual.capture_on(*halves), "body": Eager(), "adv": adv.capture_on(*halves)}
+    for g in graphs.values():  # warm-up
+        _time(g, 5)
+    times = {k: [] for k in graphs}
+    for _ in range(a.rounds):
+        for k, g in graphs.items():
+            times[k].append(_time(g, a.steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "steps": a.steps,
+           "what": {"dual": "SegDualTrainStep B=16+16 N=2048 fp32, graph replay",
+                    "body": "trainer._seg_dual_body on equal modules, eager autograd",
+                    "adv": "SegAdvTrainStep B=16+16 N=2048 fp32, graph replay"}}
+    for k in graphs:
+        out[k + "_ms"] = {"median": med[k], "min": min(times[k]), "max": max(times[k]),
+                          "rounds": times[k]}
+    out["dual_beats_body_in_every_round"] = all(d < b for d, b in zip(times["dual"],
+                                                                      times["body"]))
+    out["body_over_dual"] = med["body"] / med["dual"]
+    out["dual_over_adv_ms"] = med["dual"] - med["adv"]
+    out["losses_last"] = {"dual": [float(x) for x in dual.losses.tolist()], "body": last["v"]}
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: out[k] for k in ("dual_beats_body_in_every_round", "body_over_dual",
+                                          "dual_over_adv_ms")}
+                     | {k + "_ms": [med[k], min(times[k]), max(times[k])] for k in graphs}))
+
+
 def _regu(a):
     """--stack --regu: SegStackReguTrainStep against SegStackTrainStep."""
     import adversarial_learning_on_pointclouds_amd as pc
@@ -308,16 +386,22 @@ def main():
     ap.add_argument("--regu", action="store_true",
                     help="with --stack: time SegStackReguTrainStep against SegStackTrainStep "
                          "(profiles/segregu_bench.json)")
+    ap.add_argument("--dual", action="store_true",
+                    help="time SegDualTrainStep against the autograd body and the pointwise step "
+                         "(profiles/segdual_bench.json)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.regu and not a.stack:
         ap.error("--regu goes with --stack")
     if a.out is None:
-        a.out = os.path.join("profiles", "segadv_semi_bench.json" if a.semi else
+        a.out = os.path.join("profiles", "segdual_bench.json" if a.dual else
+                             "segadv_semi_bench.json" if a.semi else
                              "segregu_bench.json" if a.regu else
                              "segstack_bench.json" if a.stack else "segadv_bench.json")
     if not torch.cuda.is_available():
         sys.exit("segadv_bench: no HIP device (the steps are timed on the MI355X only)")
+    if a.dual:
+        return _dual(a)
     if a.semi:
         return _semi(a)
     if a.regu:
