@@ -12,7 +12,9 @@ SegAdvTrainStep (run_training_seg, and run_training_seg_semi with its
 pseudo-label term); StackDiscNet (models/discriminator.py:139-175) and
 SegStackTrainStep (run_training_seg_stack); PointNetSeg_regulization
 (models/pointnet.py:205-259) and SegStackReguTrainStep
-(run_training_seg_stack_regulization); BaseDiscNet / ShapeDiscNet /
+(run_training_seg_stack_regulization), both with the pseudo-label term
+(semi=True: run_training_seg_stack_semi,
+run_training_seg_stack_regulization_semi); BaseDiscNet / ShapeDiscNet /
 PointDiscNet (models/discriminator.py:82-137) and SegDualTrainStep
 (run_training_seg_dual); run_training_semi; the HDF5 datasets of
 dataset/modelNetData.py and dataset/shapeNetData.py without h5py, with a

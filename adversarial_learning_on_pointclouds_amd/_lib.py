@@ -159,6 +159,12 @@ class StackdiscArgs(ctypes.Structure):
     ]
 
 
+class StackdiscSemi(ctypes.Structure):
+    """Mirror of pcadv_stackdisc_semi (include/pcadv.h)."""
+
+    _fields_ = [("semi_th", _f), ("loss_semi", _vp), ("kept", _vp)]
+
+
 class DualTailArgs(ctypes.Structure):
     """Mirror of pcadv_dual_tail_args (include/pcadv.h)."""
 
@@ -264,6 +270,9 @@ SIGNATURES = {
     "pcadv_stackdisc_workspace_bytes": (_sz, [_i64, _i]),
     "pcadv_stackdisc_forward": (_i, [ctypes.POINTER(StackdiscArgs), _vp]),
     "pcadv_stackdisc_backward": (_i, [ctypes.POINTER(StackdiscArgs), _vp]),
+    "pcadv_stackdisc_forward_semi": (_i, [ctypes.POINTER(StackdiscArgs),
+                                          ctypes.POINTER(StackdiscSemi), _vp]),
+    "pcadv_row_semi_apply": (_i, [_vp, _i64, _vp, _i, _i, _f, _f, _vp, _vp, _i64, _vp, _vp]),
     "pcadv_cloud_xform_fwd": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "pcadv_cloud_xform_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i, _i, _i,
                                    _i, _vp]),

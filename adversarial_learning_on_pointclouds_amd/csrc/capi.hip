@@ -116,7 +116,7 @@ size_t pwdisc_workspace_bytes(long long, int);
 int launch_pwdisc_fwd(const pcadv_pwdisc_args*, hipStream_t);
 int launch_pwdisc_bwd(const pcadv_pwdisc_args*, hipStream_t);
 size_t stackdisc_workspace_bytes(long long, int);
-int launch_stackdisc_fwd(const pcadv_stackdisc_args*, hipStream_t);
+int launch_stackdisc_fwd(const pcadv_stackdisc_args*, const pcadv_stackdisc_semi*, hipStream_t);
 int launch_stackdisc_bwd(const pcadv_stackdisc_args*, hipStream_t);
 size_t row_ce_workspace_bytes(int);
 int launch_row_ce(const float*, long long, const int64_t*, int, int, float, float*, float*, void*,
@@ -887,7 +887,16 @@ size_t pcadv_stackdisc_workspace_bytes(int64_t rows, int max_workgroups) {
 }
 
 int pcadv_stackdisc_forward(const pcadv_stackdisc_args* args, hipStream_t stream) {
-  return launch_stackdisc_fwd(args, stream);
+  return launch_stackdisc_fwd(args, nullptr, stream);
+}
+
+int pcadv_stackdisc_forward_semi(const pcadv_stackdisc_args* args, const pcadv_stackdisc_semi* semi,
+                                 hipStream_t stream) {
+  if (!semi) {
+    set_error("pcadv_stackdisc_forward_semi: semi is NULL");
+    return PCADV_EINVAL;
+  }
+  return launch_stackdisc_fwd(args, semi, stream);
 }
 
 int pcadv_stackdisc_backward(const pcadv_stackdisc_args* args, hipStream_t stream) {

@@ -77,7 +77,13 @@ struct PwdBwdArgs {
 // four lanes per row, column c = q + 4 i.  The row max and the exp sum combine
 // the four lanes' partials by xor shuffles (commutative: every lane holds the
 // same bits), in one fixed order.
-__device__ __forceinline__ void pwd_load_x0(const PwdNet& p, int r0, int tid, float* x0) {
+// SEMI (k_stk_fwd<true>): es receives the row's sum of exp(x - max) over the
+// classes OTHER than the first maximum (semi.hip's sm_row), so that the row's
+// pseudo-label loss logsumexp - max = log1p(es) does not cancel on a confident
+// row; the same value in the row's four lanes.
+template <bool SEMI>
+__device__ __forceinline__ void pwd_load_x0_t(const PwdNet& p, int r0, int tid, float* x0,
+                                              float& es) {
   const int row = tid >> 2, q = tid & 3;
   const long long g = (long long)r0 + row;
   const bool in = g < (long long)p.n0 + p.n1;
@@ -104,6 +110,19 @@ __device__ __forceinline__ void pwd_load_x0(const PwdNet& p, int r0, int tid, fl
   }
   s += __shfl_xor(s, 1);
   s += __shfl_xor(s, 2);
+  if constexpr (SEMI) {
+    int bi = 64;  // the first class at the maximum: the lane's, then the row's
+#pragma unroll
+    for (int i = 15; i >= 0; --i)
+      if (v[i] == mx) bi = q + 4 * i;
+    bi = min(bi, __shfl_xor(bi, 1));
+    bi = min(bi, __shfl_xor(bi, 2));
+    es = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) es += q + 4 * i != bi ? e[i] : 0.f;
+    es += __shfl_xor(es, 1);
+    es += __shfl_xor(es, 2);
+  }
   const float lg = logf(s);
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
@@ -113,6 +132,10 @@ __device__ __forceinline__ void pwd_load_x0(const PwdNet& p, int r0, int tid, fl
     if (tr == PCADV_PWD_LOG_SOFTMAX) y = (v[i] - mx) - lg;
     x0[row * PD_S + c] = (in && c < p.ncls) ? y : 0.f;
   }
+}
+__device__ __forceinline__ void pwd_load_x0(const PwdNet& p, int r0, int tid, float* x0) {
+  float es;
+  pwd_load_x0_t<false>(p, r0, tid, x0, es);
 }
 
 // B fragments of W [O][ldw] for output columns [oc, oc + 32), k < kmax (zero
@@ -595,12 +618,30 @@ __device__ __forceinline__ float stk_bce(float lx, float l1x, float y) {
   return -(y * lx + (1.f - y) * l1x);
 }
 
-__global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int ntiles) {
+// The semi-supervised term's scan (run_training_seg_stack_semi, utils/trainer.py:
+// 1516-1530) in the forward's row lanes: a no-GT row is kept iff !(d_out <=
+// th), its loss is log1p(es) (pwd_load_x0_t).  Per workgroup the kept count and
+// the loss sum (f64) run in tile order into term rows 5..7 of the partials (the
+// count's bits, the sum as an f32 pair hi + lo), and the last workgroup sums
+// them in workgroup order with the other terms: K is on the device before the
+// backward runs, so the gradient needs one launch (pcadv_row_semi_apply).
+struct StkSemi {
+  float th;
+  float* loss;
+  int32_t* kept;
+};
+constexpr int SK_TK = 5, SK_THI = 6, SK_TLO = 7;  // the scan's term rows
+
+// SEMI = false is the plain forward (sm is not read).
+template <bool SEMI>
+__global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int ntiles, StkSemi sm) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   PwdFwdLds& L = *reinterpret_cast<PwdFwdLds*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long M = (long long)p.n0 + p.n1;
   const int S = o.S;
+  double ssum = 0.0;  // SEMI, wave 0: the kept rows' loss sum and count over the tiles
+  int skept = 0;
   uint32_t stepv = 0;
   if (o.losses && o.step) stepv = (uint32_t)*o.step;
   // wave 0's sums over this workgroup's tiles, in tile order: lane c < 32 holds
@@ -609,7 +650,8 @@ __global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int 
   int nbad = 0;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int r0 = tile * PD_ROWS;
-    pwd_load_x0(p, r0, tid, L.xa);
+    float es = 0.f;
+    pwd_load_x0_t<SEMI>(p, r0, tid, L.xa, es);
     __syncthreads();
     pwd_chain3<ACT_LRELU>(p, L.xa, L.xb, L.xa, L.xb, wave, lane);  // xa is free from here
     {
@@ -721,6 +763,11 @@ __global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int 
           sc[SK_CT + 2] = t_ng;
           sc[SK_CT + 3] = t_ce;
           sc[SK_CT + 4] = t_bad;
+          if constexpr (SEMI) {
+            const bool keep = in && g >= p.n0 && !(x <= sm.th);  // the x stored as d_out[g]
+            sc[SK_CT + 5] = keep ? log1pf(es) : 0.f;
+            sc[SK_CT + 6] = keep ? 1.f : 0.f;
+          }
         }
       }
     }
@@ -741,6 +788,10 @@ __global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int 
       if (wave == 0) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) t5[k] = wave_sum(L.xa[lane * PD_S + SK_CT + k]);
+        if constexpr (SEMI) {
+          ssum += (double)wave_sum(L.xa[lane * PD_S + SK_CT + 5]);
+          skept += (int)wave_sum(L.xa[lane * PD_S + SK_CT + 6]);
+        }
       }
       __syncthreads();  // the next tile's x0 goes to xa
       if (wave == 0) {
@@ -758,6 +809,12 @@ __global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int 
     o.partial[(size_t)(SK_NTERM + lane) * G + blockIdx.x] = gsum;
     if (lane < 4) o.partial[(size_t)lane * G + blockIdx.x] = tsum[lane];
     if (lane == 4) o.partial[(size_t)4 * G + blockIdx.x] = __int_as_float(nbad);
+    if constexpr (SEMI) {
+      const float hi = (float)ssum;
+      if (lane == SK_TK) o.partial[(size_t)SK_TK * G + blockIdx.x] = __int_as_float(skept);
+      if (lane == SK_THI) o.partial[(size_t)SK_THI * G + blockIdx.x] = hi;
+      if (lane == SK_TLO) o.partial[(size_t)SK_TLO * G + blockIdx.x] = (float)(ssum - (double)hi);
+    }
   }
   // the last workgroup to arrive sums the workgroups' terms in workgroup order
   __syncthreads();
@@ -802,6 +859,27 @@ __global__ void __launch_bounds__(PD_T, 2) k_stk_fwd(PwdNet p, StkFwdOut o, int 
       bad += (int)__hip_atomic_load(part + (size_t)4 * G + t, __ATOMIC_RELAXED,
                                     __HIP_MEMORY_SCOPE_AGENT);
     bad = wave_sum(bad);
+  }
+  if constexpr (SEMI) {
+    if (wave == 1) {  // the workgroups' counts and loss sums, lane-strided then a butterfly
+      int K = 0;
+      double tot = 0.0;
+      for (int t = lane; t < G; t += 64) {
+        K += (int)__hip_atomic_load(part + (size_t)SK_TK * G + t, __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+        const float hi = __uint_as_float(__hip_atomic_load(
+            part + (size_t)SK_THI * G + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        const float lo = __uint_as_float(__hip_atomic_load(
+            part + (size_t)SK_TLO * G + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        tot += (double)hi + (double)lo;
+      }
+      K = wave_sum(K);
+      tot = wave_sum(tot);
+      if (lane == 0) {
+        *sm.loss = K > 0 ? (float)(tot / (double)K) : 0.f;
+        *sm.kept = K;
+      }
+    }
   }
   __syncthreads();
   if (tid < 2 * S) (tid < S ? o.db5 : o.dw5)[tid < S ? tid : tid - S] = fin[4 + tid];
@@ -1005,12 +1083,20 @@ int launch_pwdisc_bwd(const pcadv_pwdisc_args* a, hipStream_t s) {
                                   pwd_ws((long long)a->n0 + a->n1, a->max_workgroups, false), s);
 }
 
-int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, hipStream_t s) {
-  const char* what = "pcadv_stackdisc_forward";
+// pcadv_stackdisc_forward (semi NULL) and pcadv_stackdisc_forward_semi
+int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, const pcadv_stackdisc_semi* semi,
+                         hipStream_t s) {
+  const char* what = semi ? "pcadv_stackdisc_forward_semi" : "pcadv_stackdisc_forward";
   PwdNet p;
   if (int rc = pwd_check(a, what, p)) return rc;
   const int nt = pwd_tiles((long long)a->n0 + a->n1);
   PC_REQUIRE(a->d_out, "%s: d_out is required", what);
+  if (semi) {
+    PC_REQUIRE(a->losses, "%s: the scan runs with the loss terms: losses is required", what);
+    PC_REQUIRE(semi->loss_semi && semi->kept, "%s: loss_semi and kept are required", what);
+    PC_REQUIRE(((uintptr_t)semi->loss_semi & 3) == 0 && ((uintptr_t)semi->kept & 3) == 0,
+               "%s: loss_semi and kept are not 4-B aligned", what);
+  }
   StkFwdOut o = {};
   o.w5 = a->w[4];
   o.b5 = a->b[4];
@@ -1047,10 +1133,18 @@ int launch_stackdisc_fwd(const pcadv_stackdisc_args* a, hipStream_t s) {
     o.ticket = ws.ticket(a->workspace);
     o.partial = ws.partial(a->workspace);
   }
-  static int once = pwd_lds(k_stk_fwd, sizeof(PwdFwdLds), "k_stk_fwd");  // see launch_pwdisc_fwd
+  const dim3 grid(pwd_grid(nt, a->max_workgroups, PD_FWD_WG));
+  if (semi) {
+    const StkSemi sm = {semi->semi_th, semi->loss_semi, semi->kept};
+    static int once_semi = pwd_lds(k_stk_fwd<true>, sizeof(PwdFwdLds), "k_stk_fwd<semi>");
+    if (once_semi) return once_semi;
+    hipLaunchKernelGGL(k_stk_fwd<true>, grid, dim3(PD_T), sizeof(PwdFwdLds), s, p, o, nt, sm);
+    PC_HIP_CHECK_LAUNCH("k_stk_fwd<semi>");
+    return PCADV_OK;
+  }
+  static int once = pwd_lds(k_stk_fwd<false>, sizeof(PwdFwdLds), "k_stk_fwd");  // see launch_pwdisc_fwd
   if (once) return once;
-  hipLaunchKernelGGL(k_stk_fwd, dim3(pwd_grid(nt, a->max_workgroups, PD_FWD_WG)), dim3(PD_T),
-                     sizeof(PwdFwdLds), s, p, o, nt);
+  hipLaunchKernelGGL(k_stk_fwd<false>, grid, dim3(PD_T), sizeof(PwdFwdLds), s, p, o, nt, StkSemi{});
   PC_HIP_CHECK_LAUNCH("k_stk_fwd");
   return PCADV_OK;
 }

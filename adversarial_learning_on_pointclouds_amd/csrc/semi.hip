@@ -10,6 +10,10 @@
 // every call: the workspace never needs zeroing.  The row layout is
 // k_row_eval's: sixteen lanes per row, four classes per lane.
 //
+// pcadv_row_semi_apply is the one-launch form for a caller that already holds K
+// on the device (pcadv_stackdisc_forward_semi counts it in D's forward): the
+// gradient pass alone, the same row code.
+//
 // The work per row is a handful of dependent steps (two loads, twelve
 // cross-lane exchanges, an exp and a log), so a workgroup that walked many rows
 // per slot would be bound by their latencies, not by memory: a workgroup takes
@@ -77,6 +81,28 @@ __device__ __forceinline__ void sm_row(const float* x, int c0, int ncls, float (
   for (int j = 0; j < 4; ++j) es += (c0 + j < ncls && c0 + j != bi) ? expf(v[j] - bv) : 0.f;
 #pragma unroll
   for (int o = SM_LPR / 2; o > 0; o >>= 1) es += __shfl_xor(es, o, SM_LPR);
+}
+
+// A kept row's gradient coef (softmax - onehot), added to the lane's four
+// columns of dlogits: k_row_semi_apply's statements, for k_row_semi_apply_dev
+// (that kernel keeps its own copy, so that it compiles to what it did)
+template <bool VEC>
+__device__ __forceinline__ void sm_add_grad(const RowSemi& a, int r, int c0, float coef,
+                                            const float (&v)[4], float bv, int bi, float es) {
+  const float e = 1.f + es;
+  float g[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) g[j] = coef * ((c0 + j == bi ? -es : expf(v[j] - bv)) / e);
+  float* d = a.dlogits + (size_t)r * a.ldd + c0;
+  if (VEC && c0 + 4 <= a.ncls) {
+    f32x4 t = *reinterpret_cast<f32x4*>(d);
+    t.x += g[0], t.y += g[1], t.z += g[2], t.w += g[3];
+    *reinterpret_cast<f32x4*>(d) = t;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (c0 + j < a.ncls) d[j] += g[j];
+  }
 }
 
 // Launch 1: labels_out, and the workgroup's kept count and loss sum (f64, rows
@@ -182,6 +208,34 @@ __global__ void __launch_bounds__(SM_T) k_row_semi_apply(const RowSemi a) {
   }
 }
 
+// pcadv_row_semi_apply: k_row_semi_apply's second half alone, with K read from
+// device memory (the stacked D's forward counted it, pwdisc.hip): no slot sum,
+// no workspace.  labels_out is written for every row; with K <= 0 no row counts
+// as kept (every label 255) and nothing else is written.
+template <bool VEC>
+__global__ void __launch_bounds__(SM_T) k_row_semi_apply_dev(const RowSemi a,
+                                                             const int32_t* __restrict__ kept) {
+  const int tid = threadIdx.x, sub = tid & (SM_LPR - 1), slot = tid / SM_LPR;
+  const int K = *kept;
+  const int r0 = blockIdx.x * a.rpb, r1 = min(r0 + a.rpb, a.M);
+  if (K <= 0) {
+    if (a.labels_out)
+      for (int r = r0 + tid; r < r1; r += SM_T) a.labels_out[r] = 255;
+    return;
+  }
+  const float coef = a.scale / (float)K;
+  const int c0 = 4 * sub;
+  for (int r = r0 + slot; r < r1; r += SM_SLOTS) {
+    const bool keep = !(a.d_out[r] <= a.th);
+    float v[4], bv, es;
+    int bi;
+    sm_row<VEC>(a.logits + (size_t)r * a.ld, c0, a.ncls, v, bv, bi, es);
+    if (sub == 0 && a.labels_out) a.labels_out[r] = keep ? bi : 255;
+    if (!keep) continue;
+    sm_add_grad<VEC>(a, r, c0, coef, v, bv, bi, es);
+  }
+}
+
 // rows per workgroup: the fewest (a multiple of SM_SLOTS) that keep the grid
 // within SM_MAXB workgroups
 int sm_rows_per_block(int M) {
@@ -235,6 +289,32 @@ int pcadv_row_semi_ce(const float* logits, int64_t ld, const float* d_out, int M
     hipLaunchKernelGGL(k_row_semi_apply<false>, dim3(nblk), dim3(SM_T), 0, stream, a);
   }
   PC_HIP_CHECK_LAUNCH("k_row_semi_apply");
+  return PCADV_OK;
+}
+
+int pcadv_row_semi_apply(const float* logits, int64_t ld, const float* d_out, int M, int ncls,
+                         float semi_th, float scale, const int32_t* kept, float* dlogits,
+                         int64_t ldd, int32_t* labels_out, hipStream_t stream) {
+  PC_REQUIRE(logits && d_out && dlogits && kept && M > 0 && ld >= ncls && ldd >= ncls,
+             "row_semi_apply: bad shape");
+  PC_REQUIRE(ncls >= 2 && ncls <= 4 * SM_LPR, "row_semi_apply: ncls %d outside 2..%d", ncls,
+             4 * SM_LPR);
+  PC_REQUIRE((long long)M * ld < (1LL << 40) && (long long)M * ldd < (1LL << 40),
+             "row_semi_apply: logits too large");
+  PC_REQUIRE((reinterpret_cast<uintptr_t>(kept) & 3) == 0, "row_semi_apply: kept is not 4-B aligned");
+  RowSemi a{};
+  a.logits = logits, a.ld = ld, a.d_out = d_out, a.th = semi_th, a.scale = scale;
+  a.dlogits = dlogits, a.ldd = ldd, a.labels_out = labels_out, a.M = M, a.ncls = ncls;
+  a.rpb = sm_rows_per_block(M);
+  const int nblk = (M + a.rpb - 1) / a.rpb;
+  PC_REQUIRE(nblk >= 1 && nblk <= SM_MAXB, "row_semi_apply: internal: %d workgroups", nblk);
+  const bool vec = ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) &
+                    15) == 0 && ld % 4 == 0 && ldd % 4 == 0;
+  if (vec)
+    hipLaunchKernelGGL(k_row_semi_apply_dev<true>, dim3(nblk), dim3(SM_T), 0, stream, a, kept);
+  else
+    hipLaunchKernelGGL(k_row_semi_apply_dev<false>, dim3(nblk), dim3(SM_T), 0, stream, a, kept);
+  PC_HIP_CHECK_LAUNCH("k_row_semi_apply_dev");
   return PCADV_OK;
 }
 

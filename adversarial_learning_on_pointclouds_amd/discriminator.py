@@ -37,7 +37,8 @@ from .ops import ACT_LRELU, ACT_NONE, LinearFunction
 
 __all__ = ["DeepConvDiscNet", "PointwiseDiscNet", "pwdisc_forward", "pwdisc_backward",
            "pwdisc_workspace", "PWD_NONE", "PWD_SOFTMAX", "PWD_LOG_SOFTMAX", "StackDiscNet",
-           "stackdisc_forward", "stackdisc_backward", "stackdisc_workspace", "BaseDiscNet",
+           "stackdisc_forward", "stackdisc_backward", "stackdisc_workspace", "row_semi_apply",
+           "BaseDiscNet",
            "ShapeDiscNet", "PointDiscNet"]
 
 PWD_MAX_DIM = 64  # input channels the fused kernels take (the MFMA's padded K)
@@ -197,11 +198,18 @@ def stackdisc_forward(logits, ncls, n0, n1, t0, t1, params, m, argc, d_out, ws, 
                       shape_logits=None, losses=None, shape_label=None, pts_per_cloud=0,
                       lambda_disc_shape=1.0, soft0=None, soft1=None, soft_out=None, seed=0,
                       step_count=None, dm_d=None, dm_adv=None, grads5=None, bad_rows=None,
-                      max_workgroups=0):
+                      max_workgroups=0, semi_th=None, loss_semi=None, kept=None):
     """pcadv_stackdisc_forward on the current stream (include/pcadv.h): m, argc,
     d_out, optionally shape_logits (rows, num_shapes), and, with `losses` (5
     floats), the BCE and shape terms with dm_d / dm_adv, conv5's gradients
-    grads5 = (dw5, db5) and the int32 bad_rows counter."""
+    grads5 = (dw5, db5) and the int32 bad_rows counter.
+
+    With semi_th, pcadv_stackdisc_forward_semi instead: the same outputs, and the
+    semi-supervised term's scan of the no-GT rows in the same launch: loss_semi
+    (1 float) and kept (1 int32, the number of rows with d_out above semi_th).
+    It needs `losses`."""
+    if semi_th is not None and losses is None:
+        raise ValueError("semi_th: the scan runs with the loss terms, `losses` is required")
     a = _args(_STK, logits, ncls, n0, n1, t0, t1, params, m, argc, ws, max_workgroups)
     S = a.num_shapes
     a.d_out = _vp(_f32(d_out, "d_out", n0 + n1))
@@ -225,8 +233,34 @@ def stackdisc_forward(logits, ncls, n0, n1, t0, t1, params, m, argc, d_out, ws, 
         a.dw[4] = _f32(grads5[0], "conv5's weight gradient", S).data_ptr()
         a.db[4] = _f32(grads5[1], "conv5's bias gradient", S).data_ptr()
         a.bad_rows = _vp(_i32(bad_rows, "bad_rows", 1))
+    if semi_th is not None:
+        sm = _lib.StackdiscSemi(float(semi_th), _vp(_f32(loss_semi, "loss_semi", 1)),
+                                _vp(_i32(kept, "kept", 1)))
+        check(_lib.load().pcadv_stackdisc_forward_semi(ctypes.byref(a), ctypes.byref(sm),
+                                                       stream_ptr()),
+              "pcadv_stackdisc_forward_semi")
+        return
     check(_lib.load().pcadv_stackdisc_forward(ctypes.byref(a), stream_ptr()),
           "pcadv_stackdisc_forward")
+
+
+def row_semi_apply(logits, ncls, d_out, semi_th, scale, kept, dlogits, labels_out=None):
+    """pcadv_row_semi_apply on the current stream (include/pcadv.h): with K =
+    kept[0] > 0 (device int32), scale / K (softmax - onehot(argmax)) is ADDED to
+    the rows of dlogits whose d_out is above semi_th.  logits and dlogits are
+    point-major (M, >= ncls) rows, d_out (M,); labels_out (M int32, optional)
+    receives every row's pseudo-label, 255 where ignored."""
+    M = d_out.numel()
+    for t, name in ((logits, "logits"), (dlogits, "dlogits")):
+        if t.dim() != 2 or t.shape[0] != M or t.shape[1] < ncls or t.stride(1) != 1 \
+                or t.dtype != torch.float32 or t.device.type != "cuda":
+            raise ValueError(f"{name}: expected point-major float32 ({M}, >= {ncls}) rows on the "
+                             "HIP device")
+    check(_lib.load().pcadv_row_semi_apply(
+        _vp(logits), max(logits.stride(0), ncls), _vp(_f32(d_out, "d_out", M)), M, ncls,
+        float(semi_th), float(scale), _vp(_i32(kept, "kept", 1)), _vp(dlogits),
+        max(dlogits.stride(0), ncls), None if labels_out is None else
+        _vp(_i32(labels_out, "labels_out", M)), stream_ptr()), "pcadv_row_semi_apply")
 
 
 def stackdisc_backward(logits, ncls, n0, n1, t0, t1, params, m, argc, ws, dm_d, grads, *,

@@ -38,8 +38,8 @@ import torch.nn as nn
 from . import _lib, ops
 from ._lib import check, stream_ptr
 from .discriminator import (PWD_LOG_SOFTMAX, PWD_SOFTMAX, PointwiseDiscNet, StackDiscNet,
-                            pwdisc_backward, pwdisc_forward, pwdisc_workspace, stackdisc_backward,
-                            stackdisc_forward, stackdisc_workspace)
+                            pwdisc_backward, pwdisc_forward, pwdisc_workspace, row_semi_apply,
+                            stackdisc_backward, stackdisc_forward, stackdisc_workspace)
 from .flat import FlatAdam
 from .pointnet import STN3d, STNkd
 from .step import FusedStep
@@ -937,7 +937,7 @@ class _SegDiscStep(_SegStep):
         if self.model_D.fills_rows and (B * N) % self.model_D.input_pts:
             raise ValueError(f"{B} x {N} points do not fill rows of model_D.input_pts = "
                              f"{self.model_D.input_pts}")
-        if semi and self.model_D.input_pts != N:
+        if semi and self.model_D.fills_rows and self.model_D.input_pts != N:
             raise ValueError(f"semi=True: model_D.input_pts = {self.model_D.input_pts} is not the "
                              f"clouds' {N} points (the reference's mask indexes (B, N))")
         M = B * N
@@ -1106,25 +1106,41 @@ class SegStackTrainStep(_SegDiscStep):
     line; loss_D_shape unscaled).  `bad_rows` (device int32) counts the points
     whose D output left [0, 1] in the last step: torch's BCELoss raises there,
     a captured graph cannot, so the caller checks the counter when it reads the
-    losses (`logged` does)."""
+    losses (`logged` does).
+
+    semi=True adds run_training_seg_stack_semi's term (utils/trainer.py:
+    1516-1537): lambda_semi times the cross entropy of the no-GT points whose D
+    output is above semi_th against their own argmax.  The D forward counts the
+    kept points and sums their losses in its own launch
+    (pcadv_stackdisc_forward_semi), the D backward writes the no-GT rows of
+    dlogits, and pcadv_row_semi_apply adds the term's gradient to them with the
+    count read on the device (D receives nothing from it).  Any point count is
+    allowed: this D does not use input_pts.  `losses_semi` is [loss_seg,
+    loss_adv, loss_semi, loss_D, loss_D_shape], `kept` the number of kept points
+    and, under keep_activations, `semi_labels` the pseudo-labels (255 where
+    ignored); `losses` is as above.  A captured graph has `semi` baked in:
+    capture one graph per value."""
 
     _D_NET, _d_workspace = StackDiscNet, staticmethod(stackdisc_workspace)
+    _SEMI = 9  # loss_buf[9]: loss_semi (6..8 are the regularised step's)
 
     def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
                  lambda_adv=0.01, lambda_disc_shape=1.0, lr=1e-4, lr_D=1e-4, betas=(0.9, 0.999),
-                 eps=1e-8, device="cuda", precision=None, seed=0, keep_activations=False):
+                 eps=1e-8, device="cuda", precision=None, seed=0, keep_activations=False,
+                 lambda_semi=1.0, semi_th=0.8):
         if isinstance(model_D, StackDiscNet) and model_D.num_shapes < 16:
             raise ValueError(f"model_D has {model_D.num_shapes} shape classes, cls is 16 wide")
         super().__init__(model, model_D, optimizer, optimizer_D, lambda_seg, lambda_adv, lr, lr_D,
                          betas, eps, device, precision, seed, keep_activations)
         self.lambda_disc_shape = float(lambda_disc_shape)
+        self.lambda_semi, self.semi_th = float(lambda_semi), float(semi_th)
+        self.loss_buf = torch.zeros(10, device=self.device)
         self.bad_buf = torch.zeros(1, device=self.device, dtype=torch.int32)  # loss_buf[5]: shape
+        self.kept_buf = torch.zeros(1, device=self.device, dtype=torch.int32)
         self._loss_idx = torch.tensor([0, 1, 2, 5], device=self.device)  # the log line's order
-
-    def __call__(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
-                 apply_adam=True):
-        return super().__call__(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt,
-                                apply_adam)
+        self._semi_idx = torch.tensor([0, 1, self._SEMI, 2, 5], device=self.device)
+        self.semi_labels = None
+        self._semi_stale = False
 
     def _disc(self, logits, ncls, M, N, cls_gt, d, dws, soft0, soft1, semi):
         # make_shape_label (utils/utils.py:33-38): one label per GT cloud
@@ -1134,15 +1150,38 @@ class SegStackTrainStep(_SegDiscStep):
         argc = torch.empty(2 * M, device=self.device, dtype=torch.int32)
         dm_d = torch.empty(2 * M, device=self.device)
         dm_adv = torch.empty(M, device=self.device)
+        scan = dict(semi_th=self.semi_th, loss_semi=self.loss_buf[self._SEMI:self._SEMI + 1],
+                    kept=self.kept_buf) if semi else {}
         stackdisc_forward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, m, argc,
                           d_out, dws, losses=self.loss_buf[1:6], shape_label=shape_label,
                           pts_per_cloud=N, lambda_disc_shape=self.lambda_disc_shape, soft0=soft0,
                           soft1=soft1, seed=self.seed, step_count=self.step_count, dm_d=dm_d,
-                          dm_adv=dm_adv, grads5=self.d_grad_views[8:10], bad_rows=self.bad_buf)
+                          dm_adv=dm_adv, grads5=self.d_grad_views[8:10], bad_rows=self.bad_buf,
+                          **scan)
         stackdisc_backward(logits, ncls, M, M, PWD_SOFTMAX, PWD_LOG_SOFTMAX, self.d_params, m,
                            argc, dws, dm_d, self.d_grad_views, dm_adv=dm_adv,
                            lambda_adv=self.lambda_adv, dlogits=d)
+        labels = None
+        if semi:
+            if self.keep_activations:
+                labels = torch.empty(M, device=self.device, dtype=torch.int32)
+            self._semi_grad(logits[M:], ncls, d_out[M:], d[M:], labels)
+            self._semi_stale = True
+        elif self._semi_stale:
+            # the first step without the term after one with it: loss_semi and K
+            # back to 0 (a step that never ran the term launches nothing for it)
+            self.loss_buf[self._SEMI].zero_()
+            self.kept_buf.zero_()
+            self._semi_stale = False
+        if self.keep_activations:
+            self.semi_labels = labels
         return d_out
+
+    def _semi_grad(self, logits, ncls, d_out, d, labels):
+        """The semi term's gradient on the no-GT rows, after the forward's scan
+        left K in kept_buf and the backward wrote those rows of d."""
+        row_semi_apply(logits, ncls, d_out, self.semi_th, self.lambda_semi, self.kept_buf, d,
+                       labels)
 
     @property
     def losses(self):
@@ -1152,18 +1191,32 @@ class SegStackTrainStep(_SegDiscStep):
         return self.loss_buf.index_select(0, self._loss_idx)
 
     @property
+    def losses_semi(self):
+        """`losses` with loss_semi (0 for a step without the term, or with no
+        point kept) before loss_D: the order of the semi loops' log lines."""
+        return self.loss_buf.index_select(0, self._semi_idx)
+
+    @property
+    def kept(self):
+        """The number of no-GT points the last step's semi term kept (device
+        int32; 0 for a step without the term)."""
+        return self.kept_buf[0]
+
+    @property
     def bad_rows(self):
         """The number of points whose D output was outside [0, 1] in the last
         step (device int32)."""
         return self.bad_buf[0]
 
-    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None):
-        """_SegDiscStep.capture_on (this step has no semi term).  Reading `losses`
-        launches its gather, so that stays outside the graph."""
-        return super().capture_on(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt)
+    def capture_on(self, pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt=None, soft_nogt=None,
+                   semi=False):
+        """_SegDiscStep.capture_on.  Reading `losses` launches its gather, so that
+        stays outside the graph."""
+        return super().capture_on(pts_gt, cls_gt, seg, pts_nogt, cls_nogt, soft_gt, soft_nogt,
+                                  semi)
 
     def logged(self, with_semi=False):
-        vals = self.losses.tolist()
+        vals = (self.losses_semi if with_semi else self.losses).tolist()
         if int(self.bad_rows.item()) > 0:
             raise RuntimeError("all elements of input should be between 0 and 1")
         return vals
@@ -1180,21 +1233,24 @@ class SegStackReguTrainStep(SegStackTrainStep):
 
     `losses` is [loss_seg, loss_adv, loss_regu, loss_D, loss_D_shape], the
     order of the reference's log line; loss_regu = l_gt + l_nogt, unscaled.
-    bad_rows, logged() and capture_on are the stack step's."""
+    bad_rows, logged() and capture_on are the stack step's, and so is semi=True
+    (run_training_seg_stack_regulization_semi, utils/trainer.py:1747-1775):
+    `losses_semi` is [loss_seg, loss_adv, loss_regu, loss_semi, loss_D,
+    loss_D_shape]."""
 
     _G_NET = PointNetSeg_regulization
 
     def __init__(self, model, model_D, optimizer=None, optimizer_D=None, lambda_seg=1.0,
                  lambda_adv=0.01, lambda_disc_shape=1.0, lambda_regu=0.001, lr=1e-4, lr_D=1e-4,
                  betas=(0.9, 0.999), eps=1e-8, device="cuda", precision=None, seed=0,
-                 keep_activations=False):
+                 keep_activations=False, lambda_semi=1.0, semi_th=0.8):
         super().__init__(model, model_D, optimizer, optimizer_D, lambda_seg, lambda_adv,
                          lambda_disc_shape, lr, lr_D, betas, eps, device, precision, seed,
-                         keep_activations)
+                         keep_activations, lambda_semi, semi_th)
         self.lambda_regu = float(lambda_regu)
         # loss_buf[6:8]: the two batches' regulariser losses, [8]: their sum
-        self.loss_buf = torch.zeros(9, device=self.device)
         self._loss_idx = torch.tensor([0, 1, 8, 2, 5], device=self.device)
+        self._semi_idx = torch.tensor([0, 1, 8, self._SEMI, 2, 5], device=self.device)
         self._regu_ws = None  # pcadv_tnet_mse_reg's 4 x (2B) floats, kept between steps
 
     def _g_forward(self, pts, cls, wpl):

@@ -1232,7 +1232,9 @@ def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, po
     well, :1244-1363 (the model returns (pred, x_global, trans_feat);
     args.lambda_regu x regu_loss(trans_feat trans_feat^T, I) of each batch joins
     the generator's loss): [loss_seg, loss_adv, loss_regu, loss_D, loss_D_shape],
-    loss_regu the sum of the two batches' values, unscaled."""
+    loss_regu the sum of the two batches' values, unscaled.  With a semi_loss
+    and a shape_criterion, :1457-1586 and :1680-1833 (the mask is taken on D's
+    (B, N, 1) output): loss_semi stands before loss_D in either order."""
     stack = shape_criterion is not None
 
     def regu(trans):
@@ -1257,7 +1259,8 @@ def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, po
         loss = loss + args.lambda_regu * l_regu_gt + args.lambda_regu * l_regu_nogt
     loss_semi_value = 0.0
     if semi:
-        ignore = (D_out <= args.semi_TH).squeeze(1)  # (B N / input_pts, input_pts) on (B, N)
+        # (B N / input_pts, input_pts) on (B, N); the stacked D's output is (B, N, 1)
+        ignore = (D_out <= args.semi_TH).squeeze(2 if stack else 1)
         semi_gt = torch.argmax(pred_nogt.detach(), dim=1)
         semi_gt[ignore] = 255
         if not bool(ignore.all()):  # semi_ratio != 0.0
@@ -1282,11 +1285,12 @@ def _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss, po
         loss_D_value += loss_D.item()
     optimizer.step()  # the reference steps G before D's part: D is frozen there, the same values
     optimizer_D.step()
+    with_semi = [loss_semi_value] if semi_loss is not None else []
     if regu_loss is not None:
-        return [l_seg.item(), loss_adv.item(), l_regu_gt.item() + l_regu_nogt.item(), loss_D_value,
-                loss_D_shape.item()]
+        return [l_seg.item(), loss_adv.item(), l_regu_gt.item() + l_regu_nogt.item(), *with_semi,
+                loss_D_value, loss_D_shape.item()]
     if stack:
-        return [l_seg.item(), loss_adv.item(), loss_D_value, loss_D_shape.item()]
+        return [l_seg.item(), loss_adv.item(), *with_semi, loss_D_value, loss_D_shape.item()]
     if semi_loss is None:
         return [l_seg.item(), loss_adv.item(), loss_D_value]
     return [l_seg.item(), loss_adv.item(), loss_semi_value, loss_D_value]
@@ -1314,13 +1318,19 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
     BCELoss's error (step.logged); everything else runs _seg_adv_body with the
     shape_criterion (see run_training_seg_stack).  Where the reference loops
     differ, so do these: the fused step's class and condition, the log line,
-    the tensorboard tags, and the checkpoint by accuracy that the semi loop does
-    not write; all of it is chosen here, before the loop.  With a regu_loss as
+    the tensorboard tags, and the checkpoint by accuracy that the pointwise semi
+    loop does not write; all of it is chosen here, before the loop.  With a regu_loss as
     well as a shape_criterion (run_training_seg_stack_regulization) the fused
     configuration is the stack loop's with PointNetSeg_regulization as the
     generator and a plain MSELoss (mean) as regu_loss, the step is a
     SegStackReguTrainStep, the log line gains loss_regu as its fourth field and
-    the test pass is run_testing_seg_regulization."""
+    the test pass is run_testing_seg_regulization.  With a semi_loss as well as
+    a shape_criterion (run_training_seg_stack_semi and, with a regu_loss,
+    run_training_seg_stack_regulization_semi) the fused configuration also needs
+    CrossEntropyLoss(ignore_index=255) as semi_loss, the step runs with
+    semi=True from iteration semi_start + 1, the log line gains loss_semi before
+    loss_D, tensorboard gains Loss/train_semi, and the checkpoint by accuracy is
+    written, as the reference's stacked semi loops do."""
     from .seg import SegAdvTrainStep, SegStackReguTrainStep, SegStackTrainStep
     with_semi, stack = semi_loss is not None, shape_criterion is not None
     with_regu = regu_loss is not None
@@ -1337,19 +1347,27 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
     if with_regu:
         Step, step_args = SegStackReguTrainStep, dict(lambda_disc_shape=args.lambda_disc_shape,
                                                       lambda_regu=args.lambda_regu)
-        line += 'loss_regu = {4:.3f} loss_D = {5:.3f} loss_D_shape = {6:.3f} '
-        d_tags = (('Loss/train_D', 3), ('Loss/train_D_shape', 4))  # the reference writes no regu tag
+        if with_semi:
+            line += 'loss_regu = {4:.3f} loss_semi = {5:.3f} loss_D = {6:.3f} loss_D_shape = {7:.3f} '
+            d_tags = (('Loss/train_D', 4), ('Loss/train_D_shape', 5), ('Loss/train_semi', 3))
+        else:
+            line += 'loss_regu = {4:.3f} loss_D = {5:.3f} loss_D_shape = {6:.3f} '
+            d_tags = (('Loss/train_D', 3), ('Loss/train_D_shape', 4))  # the reference writes no regu tag
     elif stack:
         Step, step_args = SegStackTrainStep, dict(lambda_disc_shape=args.lambda_disc_shape)
-        line += 'loss_D = {4:.3f} loss_D_shape = {5:.3f} '
-        d_tags = (('Loss/train_D', 2), ('Loss/train_D_shape', 3))
+        if with_semi:
+            line += 'loss_semi = {4:.3f} loss_D = {5:.3f} loss_D_shape = {6:.3f} '
+            d_tags = (('Loss/train_D', 3), ('Loss/train_D_shape', 4), ('Loss/train_semi', 2))
+        else:
+            line += 'loss_D = {4:.3f} loss_D_shape = {5:.3f} '
+            d_tags = (('Loss/train_D', 2), ('Loss/train_D_shape', 3))
     else:
         Step, step_args = SegAdvTrainStep, {}
         line += 'loss semi = {4:.3f} loss_D = {5:.3f}' if with_semi else 'loss_D = {4:.3f} '
         d_tags = (('Loss/train_disc', -1),)
-        if with_semi:
-            step_args = dict(lambda_semi=float(getattr(args, "lambda_semi", 1.0)),
-                             semi_th=float(getattr(args, "semi_TH", 0.8)))
+    if with_semi:
+        step_args = dict(step_args, lambda_semi=float(getattr(args, "lambda_semi", 1.0)),
+                         semi_th=float(getattr(args, "semi_TH", 0.8)))
 
     def save(tag):
         if step is not None:
@@ -1371,8 +1389,8 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
         # PointwiseDiscNet's rows are input_pts points each: any whole number of
         # them, but the semi loop's mask indexes (B, N), as the reference's does
         if fusable and pts.shape == pts_nogt.shape and (
-                model_D.input_pts == pts.shape[1] if with_semi
-                else stack or (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0):
+                stack or (model_D.input_pts == pts.shape[1] if with_semi
+                          else (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0)):
             if step is None:
                 step = Step(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
                             lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
@@ -1407,7 +1425,7 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
                 logger=test_logger, test_iter=i_iter, writer=writer, args=args)
             if max_seg_accu < accu:
                 max_seg_accu, max_train_epoch = accu, ep
-                if not with_semi:  # the reference's semi loop saves none by accuracy
+                if stack or not with_semi:  # the reference's pointwise semi loop saves none by accuracy
                     save("best")
             if max_test_cat_iou < cat_iou:
                 max_test_cat_iou, max_train_cat_epoch = cat_iou, ep
@@ -1514,6 +1532,63 @@ def run_training_seg_stack_regulization(trainloader_gt, trainloader_nogt, trainl
                          seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
                          train_logger, test_logger, writer, args, shape_criterion=shape_criterion,
                          regu_loss=regu_loss)
+
+
+def run_training_seg_stack_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                                targetloader_nogt_iter, testloader, testdataset, model, model_D,
+                                gan_loss, seg_loss, semi_loss, shape_criterion, optimizer,
+                                optimizer_D, history_pool_gt, history_pool_nogt, train_logger,
+                                test_logger, writer, args):
+    """utils/trainer.py:1431-1652: run_training_seg_stack plus, for i_iter >
+    args.semi_start (> 0), args.lambda_semi x semi_loss(pred_nogt,
+    argmax(pred_nogt)) over the no-GT points whose D output (the stacked D's
+    probability, (B, N, 1)) is above args.semi_TH; the rest are ignore_index 255,
+    and the term is skipped when every point is ignored.  Tensorboard tags:
+    Loss/train_seg | adv | D | D_shape | semi.  Checkpoints: epoch_{}, best,
+    best_cat_iou, best_all_iou (unlike run_training_seg_semi, the reference saves
+    by accuracy here).  The test pass is run_testing_seg.
+
+    The log line.  The reference's format string here is malformed
+    ('loss_semi = {4.:.3f} ' raises ValueError at the end of iteration 0, so
+    its loop cannot complete one iteration as written).  This loop logs what the
+    line evidently means, in the reference's field order:
+    'loss_seg = {2:.3f} loss_adv = {3:.3f} loss_semi = {4:.3f} loss_D = {5:.3f}
+    loss_D_shape = {6:.3f} '.
+
+    The fused path is run_training_seg_stack's configuration with
+    CrossEntropyLoss(ignore_index=255) as semi_loss: every iteration whose two
+    batches have the same shape is one SegStackTrainStep, with semi=True from
+    iteration semi_start + 1 (any point count).  Anything else, and a ragged
+    last batch, runs the reference's body through autograd (_seg_adv_body).  A D
+    output outside [0, 1] raises as in run_training_seg_stack."""
+    return _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                         targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
+                         seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
+                         train_logger, test_logger, writer, args, semi_loss=semi_loss,
+                         shape_criterion=shape_criterion)
+
+
+def run_training_seg_stack_regulization_semi(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                                             targetloader_nogt_iter, testloader, testdataset, model,
+                                             model_D, gan_loss, seg_loss, regu_loss, semi_loss,
+                                             shape_criterion, optimizer, optimizer_D,
+                                             history_pool_gt, history_pool_nogt, train_logger,
+                                             test_logger, writer, args):
+    """utils/trainer.py:1654-1901: run_training_seg_stack_regulization with
+    run_training_seg_stack_semi's pseudo-label term.  The log line is the
+    reference's (:1835-1850: loss_seg, loss_adv, loss_regu, loss_semi, loss_D,
+    loss_D_shape), the tensorboard tags Loss/train_seg | adv | D | D_shape |
+    semi, the checkpoints epoch_{}, best, best_cat_iou, best_all_iou, and the
+    test pass run_testing_seg_regulization.  The fused path is
+    run_training_seg_stack_regulization's configuration with
+    CrossEntropyLoss(ignore_index=255) as semi_loss: one SegStackReguTrainStep
+    per iteration with equal batch shapes, semi=True from iteration
+    semi_start + 1."""
+    return _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
+                         targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
+                         seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
+                         train_logger, test_logger, writer, args, semi_loss=semi_loss,
+                         shape_criterion=shape_criterion, regu_loss=regu_loss)
 
 
 def _seg_dual_fusable(model, sharedDisc, shapeDisc, pointDisc, optimizer, optimizer_D_shape,

@@ -888,6 +888,45 @@ size_t pcadv_stackdisc_workspace_bytes(int64_t rows, int max_workgroups);
 int pcadv_stackdisc_forward(const pcadv_stackdisc_args* args, hipStream_t stream);
 int pcadv_stackdisc_backward(const pcadv_stackdisc_args* args, hipStream_t stream);
 
+/* ---- The semi-supervised term of the stacked loops ---------------------------
+ * (run_training_seg_stack_semi, run_training_seg_stack_regulization_semi:
+ * utils/trainer.py:1516-1530, 1747-1761.)  Additions to ABI 11 (nothing
+ * existing changes; pcadv_stackdisc_args is as above).
+ *
+ * pcadv_stackdisc_forward_semi is pcadv_stackdisc_forward (the same launch
+ * count, every output above the same bits) with the term's scan in the same
+ * kernel.  losses must not be NULL.  A no-GT row is KEPT iff
+ * !(d_out[row] <= semi_th), with the d_out value the call stores (equality is
+ * ignored, a NaN is kept).  With K kept rows:
+ *   *loss_semi = (1/K) sum over kept rows of (logsumexp(row) - max(row)) of the
+ *                row's raw logits, 0 if K = 0 (n1 = 0 included),
+ *   *kept      = K (int32).
+ * The row term is log1p of the exp sum over the classes other than the first
+ * maximum; the workgroups' sums are f64, combined in workgroup order: no
+ * floating-point atomics, the same inputs leave the same bits.  The workspace is
+ * pcadv_stackdisc_workspace_bytes'; nothing needs zeroing between calls.
+ *
+ * pcadv_row_semi_apply is pcadv_row_semi_ce's gradient pass for a caller that
+ * holds K on the device: one launch, no workspace.  logits [M][ncls] (row
+ * stride ld), d_out [M], *kept = K.  With K > 0,
+ *   dlogits[r][c] += scale / K (softmax(row)[c] - [c == label])
+ * on the rows with !(d_out[r] <= semi_th), label the FIRST index of the row's
+ * maximum: the bits pcadv_row_semi_ce adds for the same K.  labels_out
+ * (optional, int32 [M]) is written for every row: the label of a kept row, 255
+ * for an ignored one; with K <= 0 no row counts as kept (every label 255) and
+ * nothing else is written.  Ignored rows and columns >= ncls are never written.
+ * 16-byte accesses where both bases and strides allow. */
+typedef struct pcadv_stackdisc_semi {
+  float semi_th;
+  float* loss_semi;
+  int32_t* kept;
+} pcadv_stackdisc_semi;
+int pcadv_stackdisc_forward_semi(const pcadv_stackdisc_args* args, const pcadv_stackdisc_semi* semi,
+                                 hipStream_t stream);
+int pcadv_row_semi_apply(const float* logits, int64_t ld, const float* d_out, int M, int ncls,
+                         float semi_th, float scale, const int32_t* kept, float* dlogits,
+                         int64_t ldd, int32_t* labels_out, hipStream_t stream);
+
 /* ---- T-Net glue of the regularised seg generator ----------------------------
  * (PointNetSeg_regulization, models/pointnet.py:205-259;
  * run_training_seg_stack_regulization, utils/trainer.py:1218-1429.)  Additive

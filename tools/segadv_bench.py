@@ -32,6 +32,16 @@ step of the same run (the conv / fc weights equal, the same 32 clouds and the
 same StackDiscNet weights), alternated the same way, into
 profiles/segregu_bench.json.
 
+--stack --semi (and --stack --regu --semi) times the stacked step with the
+stacked semi loops' term in its two forms against the same step without it,
+three graphs alternated the same way at lr 0 with a threshold that keeps about
+half the no-GT points: "fused", what the package runs (the scan inside the D
+forward, pcadv_stackdisc_forward_semi, then pcadv_row_semi_apply after the D
+backward), and "composed", put together here and not a switch in the package
+(the plain D forward, then the two-launch pcadv_row_semi_ce on d_out[M:] after
+the D backward).  Into profiles/segstack_semi_bench.json, one entry per
+generator ("stack" / "regu").
+
 --dual times run_training_seg_dual's step (SegDualTrainStep with BaseDiscNet /
 ShapeDiscNet / PointDiscNet, G's Adam and the two SGDs) as a replayed graph
 against trainer._seg_dual_body on equal modules (the reference's iteration
@@ -375,12 +385,116 @@ def _semi(a):
                       "round_spread_us": out["round_spread_us"], "kept_share": out["kept_share"]}))
 
 
+def _composed(base):
+    """`base` with the semi term composed from the existing launches: the plain D
+    forward and backward, then pcadv_row_semi_ce on the no-GT rows."""
+    import ctypes
+    from adversarial_learning_on_pointclouds_amd._lib import check, stream_ptr
+
+    class Composed(base):
+        def _disc(self, logits, ncls, M, N, cls_gt, d, dws, soft0, soft1, semi):
+            d_out = super()._disc(logits, ncls, M, N, cls_gt, d, dws, soft0, soft1, False)
+            if semi:
+                p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+                ws = torch.empty(self.lib.pcadv_row_semi_ce_workspace_bytes(M), dtype=torch.uint8,
+                                 device=self.device)
+                check(self.lib.pcadv_row_semi_ce(
+                    p(logits[M:]), logits.stride(0), p(d_out[M:]), M, ncls, self.semi_th,
+                    self.lambda_semi, p(d[M:]), d.stride(0), None, p(self.loss_buf[self._SEMI:]),
+                    p(self.kept_buf), p(ws), ws.numel(), stream_ptr()), "pcadv_row_semi_ce")
+            return d_out
+    return Composed
+
+
+def _stack_semi(a):
+    """--stack [--regu] --semi: the stacked step without the term, with the fused
+    term and with the composed term, three graphs over the same inputs and equal
+    models, alternated.  Both Adams run at lr 0, so the parameters and with them
+    the kept share stay what they are over the replays."""
+    import adversarial_learning_on_pointclouds_amd as pc
+    B, N = 16, 2048
+    rng = np.random.default_rng(0)
+    torch.manual_seed(0)
+    pts, cls, seg = _inputs(rng, 2 * B, N)
+    args = (pts[:B].contiguous(), cls[:B].contiguous(), seg[:B].contiguous(),
+            pts[B:].contiguous(), cls[B:].contiguous())
+    base = pc.SegStackReguTrainStep if a.regu else pc.SegStackTrainStep
+    G = pc.PointNetSeg_regulization if a.regu else pc.PointNetSeg
+    kw = dict(lr=0.0, lr_D=0.0, lambda_adv=0.01, lambda_disc_shape=1.0, seed=5)
+    if a.regu:
+        kw["lambda_regu"] = 0.001
+    steps = {}
+    for k, cls_ in (("plain", base), ("fused", base), ("composed", _composed(base))):
+        g, d = G(50).cuda(), pc.StackDiscNet(N, 50, 16).cuda()
+        if steps:
+            g.load_state_dict(steps["plain"].model.state_dict())
+            d.load_state_dict(steps["plain"].model_D.state_dict())
+        elif a.regu:
+            with torch.no_grad():  # the feature transform starts near the identity (--regu)
+                g.fstn.fc3.weight.mul_(0.02)
+                g.fstn.fc3.bias.mul_(0.02)
+        steps[k] = cls_(g, d, keep_activations=(k == "plain"), **kw)
+    steps["plain"](*args)
+    th = float(steps["plain"].d_out[B * N:].median().item())
+    steps["plain"].keep_activations, steps["plain"].fw, steps["plain"].d_out = False, None, None
+    steps["fused"].semi_th = steps["composed"].semi_th = th
+    graphs = {k: s.capture_on(*args, semi=(k != "plain")) for k, s in steps.items()}
+    for g in graphs.values():  # warm-up
+        _time(g, 5)
+    times = {k: [] for k in graphs}
+    for _ in range(a.rounds):
+        for k, g in graphs.items():
+            times[k].append(_time(g, a.steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+
+    def diff(x, y):
+        d = [1e3 * (p - q) for p, q in zip(times[x], times[y])]
+        return {"median_of_medians": 1e3 * (med[x] - med[y]), "per_round": d,
+                "median": statistics.median(d), "min": min(d), "max": max(d)}
+    f_c = diff("fused", "composed")
+    same = all(torch.equal(steps["fused"].grad, steps[k].grad) for k in ("composed",))
+    entry = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "steps": a.steps,
+             "what": f"{base.__name__} B=16+16 N=2048 fp32, graph replay, lr 0: semi=False, "
+                     "semi=True (fused: scan in the D forward + pcadv_row_semi_apply), semi=True "
+                     "(composed: plain D forward + pcadv_row_semi_ce), alternated",
+             "semi_th": th, "kept": {k: int(steps[k].kept.item()) for k in ("fused", "composed")},
+             "kept_share": int(steps["fused"].kept.item()) / float(B * N),
+             "fused_over_plain_us": diff("fused", "plain"),
+             "composed_over_plain_us": diff("composed", "plain"),
+             "fused_over_composed_us": f_c,
+             "fused_not_slower_rounds": sum(x <= 0 for x in f_c["per_round"]),
+             "fused_ships": sum(x <= 0 for x in f_c["per_round"]) * 2 > a.rounds,
+             "generator_gradients_bitwise_equal": bool(same),
+             "round_spread_us": {k: 1e3 * (max(v) - min(v)) for k, v in times.items()},
+             "losses_last": {k: [float(x) for x in steps[k].losses_semi.tolist()]
+                             for k in ("fused", "composed")}}
+    for k in graphs:
+        entry[k + "_ms"] = {"median": med[k], "min": min(times[k]), "max": max(times[k]),
+                            "rounds": times[k]}
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["regu" if a.regu else "stack"] = entry
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k + "_ms": med[k] for k in graphs}
+                     | {k: entry[k]["median"] for k in ("fused_over_plain_us", "composed_over_plain_us",
+                                                        "fused_over_composed_us")}
+                     | {k: entry[k] for k in ("fused_not_slower_rounds", "fused_ships", "kept_share",
+                                              "generator_gradients_bitwise_equal")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--semi", action="store_true",
-                    help="time semi=True against semi=False (profiles/segadv_semi_bench.json)")
+                    help="time semi=True against semi=False (profiles/segadv_semi_bench.json); "
+                         "with --stack [--regu]: the stacked step's fused and composed term "
+                         "(profiles/segstack_semi_bench.json)")
     ap.add_argument("--stack", action="store_true",
                     help="time SegStackTrainStep against both (profiles/segstack_bench.json)")
     ap.add_argument("--regu", action="store_true",
@@ -395,6 +509,7 @@ def main():
         ap.error("--regu goes with --stack")
     if a.out is None:
         a.out = os.path.join("profiles", "segdual_bench.json" if a.dual else
+                             "segstack_semi_bench.json" if a.semi and a.stack else
                              "segadv_semi_bench.json" if a.semi else
                              "segregu_bench.json" if a.regu else
                              "segstack_bench.json" if a.stack else "segadv_bench.json")
@@ -402,6 +517,8 @@ def main():
         sys.exit("segadv_bench: no HIP device (the steps are timed on the MI355X only)")
     if a.dual:
         return _dual(a)
+    if a.semi and a.stack:
+        return _stack_semi(a)
     if a.semi:
         return _semi(a)
     if a.regu:
