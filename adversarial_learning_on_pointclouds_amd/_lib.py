@@ -250,6 +250,8 @@ SIGNATURES = {
     "pcadv_gather_clouds_at": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _vp, ctypes.c_double,
                                     ctypes.c_double, _u64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pcadv_gather_clouds_multi": (_i, [ctypes.POINTER(GatherJob), _i, _vp]),
+    "pcadv_gather_seg_pair": (_i, [ctypes.POINTER(GatherJob), ctypes.POINTER(GatherJob), _i, _vp, _vp,
+                                   _vp, _vp]),
     "pcadv_iter_epilogue": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "pcadv_row_ce_workspace_bytes": (_sz, [_i]),
     "pcadv_row_ce": (_i, [_vp, _i64, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),

@@ -112,6 +112,8 @@ int launch_gather_clouds(const float*, int64_t, int, int, const int64_t*, int, c
 int launch_iter_epilogue(int32_t*, int, const float*, int, float*, int, int32_t*, hipStream_t);
 int check_iter_epi(const IterEpi&);
 int launch_gather_multi(const pcadv_gather_job*, int, hipStream_t);
+int launch_gather_seg_pair(const pcadv_gather_job*, const pcadv_gather_job*, int, float*, float*,
+                           int64_t*, hipStream_t);
 size_t pwdisc_workspace_bytes(long long, int);
 int launch_pwdisc_fwd(const pcadv_pwdisc_args*, hipStream_t);
 int launch_pwdisc_bwd(const pcadv_pwdisc_args*, hipStream_t);
@@ -830,6 +832,11 @@ int pcadv_gather_clouds_at(const float* src, int64_t n_src, int npts, int src_np
 
 int pcadv_gather_clouds_multi(const pcadv_gather_job* jobs, int njobs, hipStream_t stream) {
   return launch_gather_multi(jobs, njobs, stream);
+}
+
+int pcadv_gather_seg_pair(const pcadv_gather_job* gt, const pcadv_gather_job* nogt, int C,
+                          float* pts, float* cls, int64_t* seg, hipStream_t stream) {
+  return launch_gather_seg_pair(gt, nogt, C, pts, cls, seg, stream);
 }
 
 int pcadv_iter_epilogue(int32_t* counters, int ncounters, const float* losses, int nl,

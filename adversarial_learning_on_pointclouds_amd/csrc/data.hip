@@ -85,6 +85,76 @@ __global__ void __launch_bounds__(256) k_gather_multi(GatherJobs jobs) {
                j.step, j.out, j.out_lab, j.out_seg, j.cursor, j.rng_row0);
 }
 
+// The adversarial seg steps' packed input in one launch (blockIdx.y = job: 0
+// the GT split, 1 the no-GT one): pts rows [y B, y B + B) by gather_point, seg
+// from the GT job, and in one more block per job the one-hot class rows
+// cls[y B + b][0..C) - consecutive threads write consecutive floats, every
+// element written (zeros too), a cloud index outside the split leaves its row
+// as it was, like gather_point.
+struct GatherSegPair {
+  pcadv_gather_job j[2];
+  float* cls;
+  int C;
+};
+__global__ void __launch_bounds__(256) k_gather_seg_pair(GatherSegPair a) {
+  const pcadv_gather_job& j = a.j[blockIdx.y];
+  if (blockIdx.x + 1 < gridDim.x) {
+    gather_point((int64_t)blockIdx.x * 256 + threadIdx.x, j.src, j.n_src, j.npts, j.src_npts,
+                 j.order, j.B, nullptr, 0, j.src_seg, j.sigma, j.clip, nullptr, j.seed, j.step,
+                 j.out, nullptr, j.out_seg, j.cursor, j.rng_row0);
+    return;
+  }
+  const int C = a.C;
+  float* __restrict__ cls = a.cls + (size_t)blockIdx.y * j.B * C;
+  const int64_t* __restrict__ ord = j.order + (int64_t)*j.cursor * j.B;
+  for (int t = threadIdx.x; t < j.B * C; t += 256) {
+    const int b = t / C, k = t - b * C;
+    const int64_t c = ord[b];
+    if (c < 0 || c >= j.n_src) continue;
+    cls[t] = j.src_lab[c] == k ? 1.0f : 0.0f;
+  }
+}
+
+int launch_gather_seg_pair(const pcadv_gather_job* gt, const pcadv_gather_job* nogt, int C,
+                           float* pts, float* cls, int64_t* seg, hipStream_t s) {
+  PC_REQUIRE(gt && nogt && pts && cls && seg, "gather_seg_pair: a job or an output is missing");
+  GatherSegPair a{};
+  a.j[0] = *gt;
+  a.j[1] = *nogt;
+  for (int k = 0; k < 2; ++k) {
+    const pcadv_gather_job& j = a.j[k];
+    PC_REQUIRE(j.src && j.order && j.cursor && j.src_lab && j.n_src > 0 && j.B > 0 && j.npts > 0 &&
+                   j.src_npts >= j.npts,
+               "gather_seg_pair: job %d: bad arguments (n_src=%lld B=%d npts=%d src_npts=%d)", k,
+               (long long)j.n_src, j.B, j.npts, j.src_npts);
+    PC_REQUIRE(j.sigma >= 0.0 && (j.sigma == 0.0 || j.clip > 0.0),
+               "gather_seg_pair: job %d: clip must be > 0", k);
+    PC_REQUIRE(j.lab_width == 1, "gather_seg_pair: job %d: lab_width %d (one class id per cloud)",
+               k, j.lab_width);
+  }
+  PC_REQUIRE(gt->B == nogt->B && gt->npts == nogt->npts,
+             "gather_seg_pair: the jobs differ (B %d / %d, npts %d / %d)", gt->B, nogt->B, gt->npts,
+             nogt->npts);
+  PC_REQUIRE(C >= 1 && C <= 64, "gather_seg_pair: %d classes (1..64)", C);
+  PC_REQUIRE(gt->src_seg && !nogt->src_seg,
+             "gather_seg_pair: part ids go with the GT job and only with it");
+  const int64_t n = (int64_t)gt->B * gt->npts;
+  PC_REQUIRE((int64_t)gt->B * C <= INT32_MAX && n <= (int64_t)INT32_MAX * 256,
+             "gather_seg_pair: batch too large (B=%d npts=%d)", gt->B, gt->npts);
+  a.j[0].out = pts;
+  a.j[1].out = pts + n * 3;
+  a.j[0].out_seg = seg;
+  a.j[1].out_seg = nullptr;
+  a.j[0].out_lab = a.j[1].out_lab = nullptr;
+  a.cls = cls;
+  a.C = C;
+  // the last block of each job writes its one-hot rows
+  hipLaunchKernelGGL(k_gather_seg_pair, dim3((unsigned)((n + 255) / 256) + 1, 2), dim3(256), 0, s,
+                     a);
+  PC_HIP_CHECK_LAUNCH("k_gather_seg_pair");
+  return PCADV_OK;
+}
+
 int launch_gather_clouds(const float* src, int64_t n_src, int npts, int src_npts,
                          const int64_t* idx, int B, const int64_t* src_lab, int lab_width,
                          const int64_t* src_seg, double sigma, double clip, const double* noise,

@@ -384,12 +384,14 @@ class DeviceCloudLoader:
                                               j.out_seg, j.rng_row0, stream_ptr()),
               "pcadv_gather_clouds_at")
 
-    def _gather_job(self, order, cursor, out, out_lab=None, out_seg=None):
-        """The checked arguments of one gather_at as a pcadv_gather_job."""
+    def _gather_job(self, order, cursor, out, out_lab=None, out_seg=None, packed=False):
+        """The checked arguments of one gather_at as a pcadv_gather_job.  packed:
+        a job of gather_seg_pair, which writes the labels and part ids into
+        buffers of its own (no out_lab / out_seg here)."""
         lw = 0 if self.labels is None else int(self.labels.shape[1])
-        if out_lab is None and self.labels is not None:
+        if out_lab is None and self.labels is not None and not packed:
             raise ValueError("gather_at: out_lab required for a labelled split")
-        if (out_seg is None) != (self.segs is None):
+        if (out_seg is None) != (self.segs is None) and not packed:
             raise ValueError("gather_at: out_seg goes with (and only with) a part-labelled split")
         B = self.B
 
@@ -399,7 +401,7 @@ class DeviceCloudLoader:
                 raise ValueError(f"gather_at: {name} must be contiguous {dtype} {shape} on "
                                  f"{self.device} (got {t.dtype} {tuple(t.shape)} on {t.device})")
         need(out, "out", (B, self.npts, 3), torch.float32)
-        if self.labels is not None:
+        if out_lab is not None:
             need(out_lab, "out_lab", (B, lw), torch.int64)
         if out_seg is not None:
             need(out_seg, "out_seg", (B, self.npts), torch.int64)
@@ -429,3 +431,35 @@ def gather_at_multi(items):
     lib = items[0][0].lib
     check(lib.pcadv_gather_clouds_multi(jobs, len(items), stream_ptr()),
           "pcadv_gather_clouds_multi")
+
+
+def gather_seg_pair(gt_loader, nogt_loader, orders, cursors, pts, cls, seg):
+    """The adversarial seg steps' packed input from a (shapenet_gt,
+    shapenet_nogt) pair of loaders in ONE launch (pcadv_gather_seg_pair):
+    batch *cursors[k] of the epoch order orders[k] of each loader into
+    pts (2B, npts, 3) - rows [0, B) the GT batch, [B, 2B) the no-GT one, each
+    half bitwise that loader's gather_at -, the one-hot class vectors into
+    cls (2B, 1, C), every element written, and the GT part ids into seg
+    (B, npts).  The step counters and cursors are NOT advanced here."""
+    if gt_loader.kind != "shapenet_gt" or nogt_loader.kind != "shapenet_nogt":
+        raise ValueError(f"gather_seg_pair: a shapenet_gt and a shapenet_nogt loader expected "
+                         f"(got {gt_loader.kind}, {nogt_loader.kind})")
+    B, N, dev = gt_loader.B, gt_loader.npts, gt_loader.device
+    if (nogt_loader.B, nogt_loader.npts, nogt_loader.device) != (B, N, dev):
+        raise ValueError(f"gather_seg_pair: the loaders differ (B {B} / {nogt_loader.B}, npts {N} / "
+                         f"{nogt_loader.npts}, {dev} / {nogt_loader.device})")
+    C = int(gt_loader.ds.num_classes)
+    if int(nogt_loader.ds.num_classes) != C:
+        raise ValueError(f"gather_seg_pair: num_classes {C} / {nogt_loader.ds.num_classes}")
+    for t, name, shape, dtype in ((pts, "pts", (2 * B, N, 3), torch.float32),
+                                  (cls, "cls", (2 * B, 1, C), torch.float32),
+                                  (seg, "seg", (B, N), torch.int64)):
+        if t.device != dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"gather_seg_pair: {name} must be contiguous {dtype} {shape} on {dev} "
+                             f"(got {t.dtype} {tuple(t.shape)} on {t.device})")
+    jobs = [ld._gather_job(orders[k], cursors[k], pts[k * B:(k + 1) * B], packed=True)
+            for k, ld in enumerate((gt_loader, nogt_loader))]
+    P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    check(gt_loader.lib.pcadv_gather_seg_pair(ctypes.byref(jobs[0]), ctypes.byref(jobs[1]), C,
+                                              P(pts), P(cls), P(seg), stream_ptr()),
+          "pcadv_gather_seg_pair")

@@ -934,6 +934,21 @@ class _SegDiscStep(_SegStep):
         _check_dev(pts_nogt, "pts_nogt", shape=(B, N, 3))
         if seg.shape != (B, N) or seg.dtype != torch.int64 or not seg.is_contiguous():
             raise ValueError("seg: expected contiguous int64 (B, N)")
+        pts = torch.cat([pts_gt, pts_nogt])
+        cls = torch.cat([cls_gt.float().reshape(B, 1, 16), cls_nogt.float().reshape(B, 1, 16)])
+        self._run_packed(pts, cls, seg, soft_gt, soft_nogt, apply_adam, semi)
+
+    def _run_packed(self, pts, cls, seg, soft_gt=None, soft_nogt=None, apply_adam=True,
+                    semi=False):
+        """_run on the step's packed input, as dataset.gather_seg_pair writes it:
+        pts (2B, N, 3) and cls (2B, 1, 16) f32 with the GT batch in rows [0, B)
+        and the no-GT batch in rows [B, 2B), seg (B, N) int64.  _run is the two
+        concatenations and this."""
+        B, N = seg.shape
+        _check_dev(pts, "pts", shape=(2 * B, N, 3))
+        _check_dev(cls, "cls", shape=(2 * B, 1, 16))
+        if seg.dtype != torch.int64 or not seg.is_contiguous():
+            raise ValueError("seg: expected contiguous int64 (B, N)")
         if self.model_D.fills_rows and (B * N) % self.model_D.input_pts:
             raise ValueError(f"{B} x {N} points do not fill rows of model_D.input_pts = "
                              f"{self.model_D.input_pts}")
@@ -945,9 +960,7 @@ class _SegDiscStep(_SegStep):
         if _PLANES:  # every weight's planes (fp32 mode reads conv6's only)
             _engine().split(self.param, self.wph, self.wpl)
             wpl = self.wplanes
-        pts = torch.cat([pts_gt, pts_nogt])
-        cls_gt = cls_gt.float().reshape(B, 1, 16)
-        cls = torch.cat([cls_gt, cls_nogt.float().reshape(B, 1, 16)])
+        cls_gt = cls[:B]
         fw = self._g_forward(pts, cls, wpl)
         ncls = fw["dims"][2]
         logits = fw["logits"]
@@ -1029,6 +1042,7 @@ class SegAdvTrainStep(_SegDiscStep):
                          betas, eps, device, precision, seed, keep_activations)
         self.lambda_semi, self.semi_th = float(lambda_semi), float(semi_th)
         self.kept_buf = torch.zeros(1, device=self.device, dtype=torch.int32)  # loss_buf[5]: semi
+        self._semi_idx = torch.tensor([0, 1, 5, 2], device=self.device)  # the semi log line's order
         self.semi_labels = None
         self._semi_stale = False
 
@@ -1074,7 +1088,7 @@ class SegAdvTrainStep(_SegDiscStep):
     def losses_semi(self):
         """[loss_seg, loss_adv, loss_semi, loss_D] of the last step (loss_semi is
         0 for a step without the term, or with no point kept)."""
-        return self.loss_buf[[0, 1, 5, 2]]
+        return self.loss_buf.index_select(0, self._semi_idx)
 
     @property
     def kept(self):
@@ -1625,6 +1639,20 @@ class SegDualTrainStep(_SegStep):
         _check_dev(pts_nogt, "pts_nogt", shape=(B, N, 3))
         if seg.shape != (B, N) or seg.dtype != torch.int64 or not seg.is_contiguous():
             raise ValueError("seg: expected contiguous int64 (B, N)")
+        pts = torch.cat([pts_gt, pts_nogt])
+        cls = torch.cat([cls_gt.float().reshape(B, 1, 16), cls_nogt.float().reshape(B, 1, 16)])
+        self._run_packed(pts, cls, seg, soft_gt, soft_nogt, apply_adam)
+
+    def _run_packed(self, pts, cls, seg, soft_gt=None, soft_nogt=None, apply_adam=True):
+        """_run on the step's packed input, as dataset.gather_seg_pair writes it:
+        pts (2B, N, 3) and cls (2B, 1, 16) f32 with the GT batch in rows [0, B)
+        and the no-GT batch in rows [B, 2B), seg (B, N) int64.  _run is the two
+        concatenations and this."""
+        B, N = seg.shape
+        _check_dev(pts, "pts", shape=(2 * B, N, 3))
+        _check_dev(cls, "cls", shape=(2 * B, 1, 16))
+        if seg.dtype != torch.int64 or not seg.is_contiguous():
+            raise ValueError("seg: expected contiguous int64 (B, N)")
         if (B * N) % int(self.pointDisc.input_pts):
             raise ValueError(f"{B} x {N} points do not fill rows of pointDisc.input_pts = "
                              f"{self.pointDisc.input_pts}")
@@ -1633,9 +1661,7 @@ class SegDualTrainStep(_SegStep):
         if _PLANES:
             _engine().split(self.param, self.wph, self.wpl)
             wpl = self.wplanes
-        pts = torch.cat([pts_gt, pts_nogt])
-        cls_gt = cls_gt.float().reshape(B, 1, 16)
-        cls = torch.cat([cls_gt, cls_nogt.float().reshape(B, 1, 16)])
+        cls_gt = cls[:B]
         fw = seg_forward(pts, cls, self.params, wplanes=wpl, precision=self.precision)
         ncls = fw["dims"][2]
         logits = fw["logits"]

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from .discriminator import DeepConvDiscNet
 from .metric import batch_get_iou, object_names
 from .pointnet import PointNetCls, feature_transform_regularizer
-from .dataset import gather_at_multi
+from .dataset import gather_at_multi, gather_seg_pair
 from .flat import capture_graphs
 from .step import AdvFtTrainStep, AdvTrainStep
 from .utils import make_D_label, make_shape_label
@@ -120,12 +120,16 @@ class _LossRing:
     host memory is queued, and the lines are emitted in iteration order once
     a copy has landed (polled every iteration; drained before test passes,
     checkpoints, autograd iterations and at the end).  The lines and scalars
-    are the reference's, written a few iterations late."""
+    are the reference's, written a few iterations late.  block_at_flush: wait
+    for each copy where it is queued, so a line is emitted no later than
+    slots / 2 iterations after its own (the stacked seg loops, whose emit raises
+    on a bad D output; one host wait per slots / 2 iterations)."""
 
-    def __init__(self, emit, nl, device, slots=64):
+    def __init__(self, emit, nl, device, slots=64, block_at_flush=False):
         from . import _lib
         self.lib = _lib.load()
         self.emit, self.nl, self.slots, self.half = emit, nl, slots, slots // 2
+        self.block_at_flush = bool(block_at_flush)
         self.ring = torch.zeros(slots, nl, device=device)
         self.count = torch.zeros(1, dtype=torch.int32, device=device)
         self.n_written = 0          # host mirror of *count
@@ -149,7 +153,10 @@ class _LossRing:
         if log:
             self.pending.append((slot, i_iter, extra))
         if self.n_written % self.half == 0:
-            self.flush()
+            if self.block_at_flush:
+                self.drain()
+            else:
+                self.flush()
         self.poll()
 
     def flush(self):
@@ -419,6 +426,88 @@ class _SegGraphedIteration(_GraphedIteration):
         self.oh.scatter_(2, self.lab[:, :1].unsqueeze(1), 1.0)  # one_hot (shapeNetData.py)
         self.step(self.pts[0], self.oh, self.seg)
         self.ring.write(self.step.loss.view(1), self.counters, 2)
+
+
+class _SegPairIteration(_GraphedIteration):
+    """One iteration of the adversarial segmentation loops (run_training_seg*,
+    run_training_seg_dual) fed by a (shapenet_gt, shapenet_nogt) pair of
+    DeviceCloudLoaders as ONE HIP graph: both batches, the one-hot class
+    vectors and the GT part ids gathered at the two device cursors straight
+    into the step's packed input (dataset.gather_seg_pair, one launch), the
+    step's _run_packed with `semi` baked in per graph, the loss line's values
+    gathered into one device vector, and the iteration epilogue (the loaders'
+    RNG steps and cursors += 1, the vector into the loss ring).
+
+    The vector is the loop's log line in its order - step.losses, or
+    step.losses_semi for a loop with a semi_loss - then, for the stacked steps,
+    bad_rows, and, for a loop with a semi_loss, kept (both as floats; the
+    layout is one per loop, so a graph without the term writes kept = 0).
+
+    The class ids of both splits are read once here: one outside [0, 16)
+    raises IndexError, as the reference's one_hot would on its first item."""
+
+    def __init__(self, step, loaders, ring, optimizers=(), with_semi=False):
+        gt, ng = loaders
+        for ld in loaders:
+            lo, hi = (int(v) for v in torch.aminmax(ld.labels))
+            if lo < 0 or hi >= 16:
+                raise IndexError(f"{ld.kind} loader: class ids must lie in [0, 16) for the one-hot "
+                                 f"class vector (min {lo}, max {hi})")
+        step.B, step.N = gt.B, gt.npts  # the static batch shape
+        super().__init__(step, loaders, ring, optimizers)
+        B, N, dev = gt.B, gt.npts, step.device
+        del self.lab
+        self.pts = torch.zeros(2 * B, N, 3, device=dev)  # [GT; no-GT]
+        self.cls = torch.zeros(2 * B, 1, 16, device=dev)
+        self.seg = torch.zeros(B, N, dtype=torch.int64, device=dev)
+        self.with_semi = bool(with_semi)
+        self.vec = torch.zeros(ring.nl, device=dev)
+
+    @staticmethod
+    def layout(step_class, with_semi):
+        """(values in the log line, index of bad_rows or None, index of kept or
+        None, length) of the ring vector of a loop over `step_class`."""
+        from .seg import SegDualTrainStep, SegStackReguTrainStep, SegStackTrainStep
+        n = (4 if step_class is SegDualTrainStep else
+             5 if step_class is SegStackReguTrainStep else
+             4 if step_class is SegStackTrainStep else 3) + (1 if with_semi else 0)
+        bad = n if issubclass(step_class, SegStackTrainStep) else None
+        k = n + (bad is not None)
+        return n, bad, (k if with_semi else None), k + (1 if with_semi else 0)
+
+    def replay(self, semi=False):
+        """Replay only: reading step.losses would launch its gather."""
+        self._check_hyper()
+        self._graph(semi).replay()
+
+    def _body(self, semi):
+        st, L = self.step, self.L
+        gather_seg_pair(self.loaders[0], self.loaders[1], self.order,
+                        [self.counters[L:L + 1], self.counters[L + 1:L + 2]], self.pts, self.cls,
+                        self.seg)
+        st._run_packed(self.pts, self.cls, self.seg, **({"semi": True} if semi else {}))
+        n, bad, kept, _ = self.layout(type(st), self.with_semi)
+        self.vec[:n].copy_(st.losses_semi if self.with_semi else st.losses)
+        if bad is not None:
+            self.vec[bad:bad + 1].copy_(st.bad_buf)
+        if kept is not None:
+            self.vec[kept:kept + 1].copy_(st.kept_buf)
+        self.ring.write(self.vec, self.counters, 2 * L)
+
+
+def _seg_pair_loaders(args, gt, ng):
+    """Whether a seg GAN loop's two train loaders feed _SegPairIteration: the
+    graphs are wanted (args.use_graph, default on), both are one-process
+    DeviceCloudLoaders, of kind shapenet_gt / shapenet_nogt, with equal B and
+    npts on args.device."""
+    from .dataset import DeviceCloudLoader
+    if not bool(getattr(args, "use_graph", True)):
+        return False
+    if not (isinstance(gt, DeviceCloudLoader) and isinstance(ng, DeviceCloudLoader)):
+        return False
+    return (gt.kind == "shapenet_gt" and ng.kind == "shapenet_nogt" and gt.world == ng.world == 1
+            and gt.B == ng.B and gt.npts == ng.npts and gt.device == ng.device
+            and gt.ds.num_classes == ng.ds.num_classes == 16)
 
 
 def _dp_world(*loaders):
@@ -1330,7 +1419,33 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
     CrossEntropyLoss(ignore_index=255) as semi_loss, the step runs with
     semi=True from iteration semi_start + 1, the log line gains loss_semi before
     loss_D, tensorboard gains Loss/train_semi, and the checkpoint by accuracy is
-    written, as the reference's stacked semi loops do."""
+    written, as the reference's stacked semi loops do.
+
+    The graph-fed path.  When the fused configuration holds, args.use_graph is
+    not false, both train loaders are one-process DeviceCloudLoaders of kind
+    shapenet_gt / shapenet_nogt with equal B and npts, and (B, npts) meets the
+    step's shape condition above, every iteration whose two batches are full
+    is ONE HIP graph replay (_SegPairIteration: pcadv_gather_seg_pair at the two
+    device cursors, the step's _run_packed with `semi` baked in per graph, the
+    log line's values into the device loss ring) and nothing is read on the
+    host: the lines and tensorboard scalars are the same, in iteration order,
+    written up to half a ring (32 iterations) late, every args.log_every
+    iterations (default 1).  The iterator arguments are ignored on this path:
+    the loaders' own epoch orders (epoch_order(), the draws iterating them
+    would make) feed the graph, each loader wrapping on its own.  Ragged
+    batches are gathered eagerly from the same orders and take the step's eager
+    call if the two shapes still agree, else the autograd body, as on the
+    other path.  The ring is drained before every test pass and checkpoint,
+    before an autograd iteration and at the end; an optimizer's changed lr /
+    betas / eps drops the graphs and recaptures.  Class ids outside [0, 16)
+    raise IndexError when the path is set up (the reference's one_hot would on
+    its first such item).  The one visible difference from the eager loop: the
+    stacked loops' RuntimeError on a D output outside [0, 1] is raised when the
+    iteration's ring row is read, at most 32 iterations after the bad one (or
+    at the next drain), naming it; the updates in between have run.  Every
+    other combination of loaders (torch DataLoaders, lists, sharded loaders,
+    unequal B), use_graph = False, ImagePool(pool_size > 0) and data
+    parallelism run as before."""
     from .seg import SegAdvTrainStep, SegStackReguTrainStep, SegStackTrainStep
     with_semi, stack = semi_loss is not None, shape_criterion is not None
     with_regu = regu_loss is not None
@@ -1375,49 +1490,95 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
         torch.save(model.state_dict(), os.path.join(args.exp_dir, "model_train_{}.pth".format(tag)))
         torch.save(model_D.state_dict(), os.path.join(args.exp_dir, "modelD_train_{}.pth".format(tag)))
 
-    for i_iter in range(args.total_iterations):
-        model.train()
-        model_D.train()
-        batch, trainloader_gt_iter = _next(trainloader_gt, trainloader_gt_iter)
-        pts, cls, seg = batch
-        pts, cls, seg = pts.float().to(args.device), cls.float().to(args.device), \
-            seg.long().to(args.device)
-        batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
-        pts_nogt, cls_nogt = batch
-        pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
-        semi = with_semi and args.semi_start > 0 and i_iter > args.semi_start
+    def fused_shape(B, N):
         # PointwiseDiscNet's rows are input_pts points each: any whole number of
         # them, but the semi loop's mask indexes (B, N), as the reference's does
-        if fusable and pts.shape == pts_nogt.shape and (
-                stack or (model_D.input_pts == pts.shape[1] if with_semi
-                          else (pts.shape[0] * pts.shape[1]) % model_D.input_pts == 0)):
-            if step is None:
-                step = Step(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
-                            lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
-                            device=args.device, seed=int(getattr(args, "seed", 0) or 0),
-                            **step_args)
-            elif eager_since:
-                step.after_eager()
-            eager_since = False
-            step.sync_hyper()
-            step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
-                 cls_nogt.contiguous(), **({"semi": True} if semi else {}))
-            vals = step.logged(with_semi)
-        else:
-            if step is not None:
-                step.sync_optimizer_state()
-            eager_since = True
-            vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
-                                 history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
-                                 cls_nogt, args, semi_loss=semi_loss, semi=semi,
-                                 shape_criterion=shape_criterion, regu_loss=regu_loss)
-        train_logger.info(line.format(i_iter, args.total_iterations, *vals))
+        return stack or (model_D.input_pts == N if with_semi
+                         else (B * N) % model_D.input_pts == 0)
+
+    def fused_step():
+        nonlocal step, eager_since
+        if step is None:
+            step = Step(model, model_D, optimizer=optimizer, optimizer_D=optimizer_D,
+                        lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
+                        device=args.device, seed=int(getattr(args, "seed", 0) or 0),
+                        **step_args)
+        elif eager_since:
+            step.after_eager()
+        eager_since = False
+        return step
+
+    nline, bad_at, _, nring = _SegPairIteration.layout(Step, with_semi)
+
+    def emit(i_iter, vals, extra=None):
+        # a ring row carries bad_rows (the stacked steps) behind the line's values
+        if bad_at is not None and len(vals) > bad_at and vals[bad_at] > 0:
+            raise RuntimeError("all elements of input should be between 0 and 1 (D's output at "
+                               "{} points of iteration {})".format(int(vals[bad_at]), i_iter))
+        train_logger.info(line.format(i_iter, args.total_iterations, *vals[:nline]))
         if tb:
             writer.add_scalar('Loss/train_seg', vals[0], i_iter)
             writer.add_scalar('Loss/train_adv', vals[1], i_iter)
             for tag, k in d_tags:
-                writer.add_scalar(tag, vals[k], i_iter)
+                writer.add_scalar(tag, vals[:nline][k], i_iter)
+
+    # the graph-fed path: both train loaders resident ShapeNet DeviceCloudLoaders
+    # of one batch shape that the fused step takes (_SegPairIteration)
+    graphed = bool(fusable) and _seg_pair_loaders(args, trainloader_gt, trainloader_nogt) \
+        and bool(fused_shape(trainloader_gt.B, trainloader_gt.npts))
+    gi = ring = None
+    log_every = max(1, int(getattr(args, "log_every", 1))) if graphed else 1
+    if graphed:
+        ring = _LossRing(emit, nring, args.device, block_at_flush=stack)
+
+    for i_iter in range(args.total_iterations):
+        model.train()
+        model_D.train()
+        semi = with_semi and args.semi_start > 0 and i_iter > args.semi_start
+        vals = None
+        if graphed:
+            if gi is None:
+                gi = _SegPairIteration(fused_step(), (trainloader_gt, trainloader_nogt), ring,
+                                       optimizers=(optimizer, optimizer_D), with_semi=with_semi)
+            bt = gi.next_batches()
+            if all(size == trainloader_gt.B for _, size in bt):
+                fused_step()
+                gi.replay(semi)
+                ring.record(i_iter, None, log=i_iter % log_every == 0)
+                pts = None
+            else:  # a ragged batch among the two: gathered eagerly from the same epoch orders
+                (pts, cls, seg), (pts_nogt, cls_nogt) = gi.eager_batches(bt)
+        else:
+            batch, trainloader_gt_iter = _next(trainloader_gt, trainloader_gt_iter)
+            pts, cls, seg = batch
+            batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
+            pts_nogt, cls_nogt = batch
+        if pts is not None:
+            pts, cls, seg = pts.float().to(args.device), cls.float().to(args.device), \
+                seg.long().to(args.device)
+            pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
+            if fusable and pts.shape == pts_nogt.shape and fused_shape(pts.shape[0], pts.shape[1]):
+                fused_step().sync_hyper()
+                step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
+                     cls_nogt.contiguous(), **({"semi": True} if semi else {}))
+                vals = step.logged(with_semi)
+            else:
+                if ring is not None:
+                    ring.drain()
+                if step is not None:
+                    step.sync_optimizer_state()
+                eager_since = True
+                vals = _seg_adv_body(model, model_D, optimizer, optimizer_D, gan_loss, seg_loss,
+                                     history_pool_gt, history_pool_nogt, pts, cls, seg, pts_nogt,
+                                     cls_nogt, args, semi_loss=semi_loss, semi=semi,
+                                     shape_criterion=shape_criterion, regu_loss=regu_loss)
+            if ring is None:
+                emit(i_iter, vals)
+            elif i_iter % log_every == 0:
+                ring.emit_now(i_iter, vals)
         if i_iter % args.iter_test_epoch == 0:
+            if ring is not None:
+                ring.drain()
             ep = i_iter // args.iter_test_epoch
             save("epoch_{}".format(ep))
             accu, _, cat_iou, all_iou = testing(
@@ -1433,6 +1594,8 @@ def _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter, targetl
             if max_test_all_iou < all_iou:
                 max_test_all_iou, max_train_all_epoch = all_iou, ep
                 save("best_all_iou")
+    if ring is not None:
+        ring.drain()
     if step is not None:
         step.sync_optimizer_state()
     train_logger.info("=========================")
@@ -1499,7 +1662,11 @@ def run_training_seg_stack(trainloader_gt, trainloader_nogt, trainloader_gt_iter
     device, and this loop raises RuntimeError("all elements of input should be
     between 0 and 1") when it reads the iteration's losses for the log line.
     The one difference from the eager body: that iteration's two Adam updates
-    have already run when the error is raised."""
+    have already run when the error is raised.  On the graph-fed path
+    (_seg_adv_loop: two ShapeNet DeviceCloudLoaders) the losses are read from
+    the device ring, so the error, which names the iteration, is raised at
+    most half a ring (32 iterations) after it, or at the next drain; the
+    iterations in between have run too."""
     return _seg_adv_loop(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
                          targetloader_nogt_iter, testloader, testdataset, model, model_D, gan_loss,
                          seg_loss, optimizer, optimizer_D, history_pool_gt, history_pool_nogt,
@@ -1705,7 +1872,14 @@ def run_training_seg_dual(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
     In the configuration of _seg_dual_fusable every iteration whose two batches
     have the same shape and fill rows of pointDisc.input_pts is one
     SegDualTrainStep; anything else, and a ragged last batch, runs
-    _seg_dual_body.  Returns (max_seg_accu, max_test_cat_iou, max_test_all_iou)."""
+    _seg_dual_body.  Over a (shapenet_gt, shapenet_nogt) pair of one-process
+    DeviceCloudLoaders with equal B and npts (args.use_graph not false) every
+    full iteration is one HIP graph replay with no host read, as described in
+    _seg_adv_loop (the graph-fed path): the loaders' own epoch orders, the log
+    lines up to 32 iterations late, the ring drained before test passes,
+    checkpoints, autograd iterations and at the end, a recapture when G's Adam
+    or either SGD changes its lr.  Returns (max_seg_accu, max_test_cat_iou,
+    max_test_all_iou)."""
     from .seg import SegDualTrainStep
     max_seg_accu = max_test_cat_iou = max_test_all_iou = float("-inf")
     max_train_epoch = max_train_cat_epoch = max_train_all_epoch = 0
@@ -1726,47 +1900,85 @@ def run_training_seg_dual(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
             torch.save(net.state_dict(),
                        os.path.join(args.exp_dir, "{}_train_{}{}".format(name, tag, d_suffix)))
 
-    for i_iter in range(args.total_iterations):
-        model.train()
-        for _, net in nets:
-            net.train()
-        batch, trainloader_gt_iter = _next(trainloader_gt, trainloader_gt_iter)
-        pts, cls, seg = batch
-        pts, cls, seg = pts.float().to(args.device), cls.float().to(args.device), \
-            seg.long().to(args.device)
-        batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
-        pts_nogt, cls_nogt = batch
-        pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
-        if fusable and pts.shape == pts_nogt.shape \
-                and (pts.shape[0] * pts.shape[1]) % int(pointDisc.input_pts) == 0:
-            if step is None:
-                step = SegDualTrainStep(
-                    model, sharedDisc, shapeDisc, pointDisc, optimizer=optimizer,
-                    optimizer_D_shape=optimizer_D_shape, optimizer_D_point=optimizer_D_point,
-                    lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
-                    lambda_disc_shape=args.lambda_disc_shape, device=args.device,
-                    seed=int(getattr(args, "seed", 0) or 0))
-            elif eager_since:
-                step.after_eager()
-            eager_since = False
-            step.sync_hyper()
-            step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
-                 cls_nogt.contiguous())
-            vals = step.logged()
-        else:
-            if step is not None:
-                step.sync_optimizer_state()
-            eager_since = True
-            vals = _seg_dual_body(model, sharedDisc, shapeDisc, pointDisc, optimizer,
-                                  optimizer_D_shape, optimizer_D_point, gan_point_loss,
-                                  gan_shape_loss, seg_loss, history_pool_gt, history_pool_nogt,
-                                  pts, cls, seg, pts_nogt, cls_nogt, args)
+    def fused_step():
+        nonlocal step, eager_since
+        if step is None:
+            step = SegDualTrainStep(
+                model, sharedDisc, shapeDisc, pointDisc, optimizer=optimizer,
+                optimizer_D_shape=optimizer_D_shape, optimizer_D_point=optimizer_D_point,
+                lambda_seg=args.lambda_seg, lambda_adv=args.lambda_adv,
+                lambda_disc_shape=args.lambda_disc_shape, device=args.device,
+                seed=int(getattr(args, "seed", 0) or 0))
+        elif eager_since:
+            step.after_eager()
+        eager_since = False
+        return step
+
+    def emit(i_iter, vals, extra=None):
         train_logger.info(line.format(i_iter, args.total_iterations, *vals))
         if tb:
             for tag, v in zip(('Loss/train_seg', 'Loss/train_adv', 'Loss/disc_point',
                                'Loss/disc_shape'), vals):
                 writer.add_scalar(tag, v, i_iter)
+
+    # the graph-fed path (_SegPairIteration), as in _seg_adv_loop
+    graphed = bool(fusable) and _seg_pair_loaders(args, trainloader_gt, trainloader_nogt) \
+        and (trainloader_gt.B * trainloader_gt.npts) % int(pointDisc.input_pts) == 0
+    gi = ring = None
+    log_every = max(1, int(getattr(args, "log_every", 1))) if graphed else 1
+    if graphed:
+        ring = _LossRing(emit, _SegPairIteration.layout(SegDualTrainStep, False)[3], args.device)
+
+    for i_iter in range(args.total_iterations):
+        model.train()
+        for _, net in nets:
+            net.train()
+        vals = None
+        if graphed:
+            if gi is None:
+                gi = _SegPairIteration(
+                    fused_step(), (trainloader_gt, trainloader_nogt), ring,
+                    optimizers=(optimizer, optimizer_D_shape, optimizer_D_point))
+            bt = gi.next_batches()
+            if all(size == trainloader_gt.B for _, size in bt):
+                fused_step()
+                gi.replay()
+                ring.record(i_iter, None, log=i_iter % log_every == 0)
+                pts = None
+            else:  # a ragged batch among the two: gathered eagerly from the same epoch orders
+                (pts, cls, seg), (pts_nogt, cls_nogt) = gi.eager_batches(bt)
+        else:
+            batch, trainloader_gt_iter = _next(trainloader_gt, trainloader_gt_iter)
+            pts, cls, seg = batch
+            batch, targetloader_nogt_iter = _next(trainloader_nogt, targetloader_nogt_iter)
+            pts_nogt, cls_nogt = batch
+        if pts is not None:
+            pts, cls, seg = pts.float().to(args.device), cls.float().to(args.device), \
+                seg.long().to(args.device)
+            pts_nogt, cls_nogt = pts_nogt.float().to(args.device), cls_nogt.float().to(args.device)
+            if fusable and pts.shape == pts_nogt.shape \
+                    and (pts.shape[0] * pts.shape[1]) % int(pointDisc.input_pts) == 0:
+                fused_step().sync_hyper()
+                step(pts.contiguous(), cls.contiguous(), seg.contiguous(), pts_nogt.contiguous(),
+                     cls_nogt.contiguous())
+                vals = step.logged()
+            else:
+                if ring is not None:
+                    ring.drain()
+                if step is not None:
+                    step.sync_optimizer_state()
+                eager_since = True
+                vals = _seg_dual_body(model, sharedDisc, shapeDisc, pointDisc, optimizer,
+                                      optimizer_D_shape, optimizer_D_point, gan_point_loss,
+                                      gan_shape_loss, seg_loss, history_pool_gt, history_pool_nogt,
+                                      pts, cls, seg, pts_nogt, cls_nogt, args)
+            if ring is None:
+                emit(i_iter, vals)
+            elif i_iter % log_every == 0:
+                ring.emit_now(i_iter, vals)
         if i_iter % args.iter_test_epoch == 0:
+            if ring is not None:
+                ring.drain()
             ep = i_iter // args.iter_test_epoch
             train_logger.info("======= Testing on Epoch {} =======".format(ep))
             save("epoch_{}".format(ep), ".pth")
@@ -1781,6 +1993,8 @@ def run_training_seg_dual(trainloader_gt, trainloader_nogt, trainloader_gt_iter,
             if max_test_all_iou < all_iou:
                 max_test_all_iou, max_train_all_epoch = all_iou, ep
                 save("best_all_iou", "")
+    if ring is not None:
+        ring.drain()
     if step is not None:
         step.sync_optimizer_state()
     train_logger.info("=========================")

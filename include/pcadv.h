@@ -481,6 +481,22 @@ typedef struct pcadv_gather_job {
 } pcadv_gather_job;
 int pcadv_gather_clouds_multi(const pcadv_gather_job* jobs, int njobs, hipStream_t stream);
 
+/* The adversarial segmentation steps' packed input in ONE launch, from a GT and
+ * a no-GT ShapeNet split (both jobs: the same B and npts, lab_width 1, each its
+ * own order / cursor / seed / step / sigma / clip / rng_row0; their out,
+ * out_lab and out_seg fields are not read):
+ *   pts [2B][npts][3]: rows [0, B) the GT job's batch, rows [B, 2B) the no-GT
+ *     job's, each half bitwise what pcadv_gather_clouds_at writes for that job;
+ *   cls [2B][1][C] f32: the one-hot of each cloud's class id, every element
+ *     written (no clearing launch needed); 1 <= C <= 64;
+ *   seg [B][npts] int64: the GT job's part ids (the GT job must have src_seg,
+ *     the no-GT job none).
+ * A cloud index outside its split leaves that row of all three outputs as it
+ * was.  Class ids must lie in [0, C) (checked once by the caller; an id outside
+ * gives an all-zero row).  An addition to ABI version 11. */
+int pcadv_gather_seg_pair(const pcadv_gather_job* gt, const pcadv_gather_job* nogt, int C,
+                          float* pts, float* cls, int64_t* seg, hipStream_t stream);
+
 /* The end of a graph-replayed training iteration (trainer.py): counters[i] += 1
  * for i < ncounters (<= 64: loaders' RNG steps and batch cursors), and, when
  * ring is given, losses[0..nl) (nl <= 32) into slot (*ring_count % slots) of the [slots][nl]

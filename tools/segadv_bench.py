@@ -48,6 +48,20 @@ against trainer._seg_dual_body on equal modules (the reference's iteration
 through autograd and torch's own kernels, eager: it reads its losses on the
 host as the reference does), with the pointwise adversarial step for scale,
 alternated the same way, into profiles/segdual_bench.json.
+
+--loop NAME[,NAME...] (seg, stack, regu, dual, or all) times the loops users
+call - run_training_seg, _seg_stack, _seg_stack_regulization, _seg_dual - over
+two ShapeNet DeviceCloudLoaders built from synthetic resident splits (256
+clouds each, B = 16, N = 2048, no files), wall clock per iteration.  The test
+pass and the checkpoint writes are stubbed out; the stub synchronizes the
+device and takes the time at iterations 0, K and 2K (--iters K), and the figure
+is the second interval's, so the first one absorbs the set-up (the steps'
+construction, the graph captures).  One JSON line per loop goes to stdout (and
+is appended to --jsonl).  --root DIR imports the package from another tree (the
+parent commit built into ablib/): a comparison alternates
+fresh processes of the two trees.  --step-graphs adds each step's own captured
+time (capture_on, replayed between device events).  --loop-report FILES...
+turns the collected lines into profiles/seg_loops_graph_bench.json.
 """
 import argparse
 import json
@@ -487,6 +501,198 @@ def _stack_semi(a):
                                               "generator_gradients_bitwise_equal")}))
 
 
+LOOPS = ("seg", "stack", "regu", "dual")
+
+
+def _synthetic_split(D, cls, n, npts, seed):
+    """An in-memory ShapeNet split: no file is read."""
+    rng = np.random.default_rng(seed)
+    ds = object.__new__(cls)
+    ds.num_classes, ds.npts = 16, npts
+    ds.select_data = rng.uniform(-1, 1, (n, npts, 3)).astype(np.float32)
+    ds.select_labels = rng.integers(0, 16, (n, 1)).astype(np.int64)
+    if cls is D.ShapeNetDatasetGT:
+        ds.select_segs = rng.integers(0, 50, (n, npts)).astype(np.int64)
+    return ds
+
+
+def _loop_nets(pc, name, N):
+    """(G, [D nets]) with D's biases zero and its weights Xavier: the stacked
+    D's output then starts, and at the lr used here stays, inside [0, 1]."""
+    G = (pc.PointNetSeg_regulization(50) if name == "regu" else pc.PointNetSeg(50)).cuda()
+    if name == "dual":
+        Ds = [pc.BaseDiscNet(N, 50, 256), pc.ShapeDiscNet(256, 16), pc.PointDiscNet(256, N)]
+    else:
+        Ds = [pc.PointwiseDiscNet(N, 50) if name == "seg" else pc.StackDiscNet(N, 50, 16)]
+    Ds = [d.cuda() for d in Ds]
+    with torch.no_grad():
+        for d in Ds:
+            for k, p in d.named_parameters():
+                if k.endswith("bias"):
+                    p.zero_()
+                elif p.dim() > 1:
+                    torch.nn.init.xavier_uniform_(p)
+    return G, Ds
+
+
+def _loop_opts(name, G, Ds, lr):
+    opt = torch.optim.Adam(G.parameters(), lr=lr)
+    if name == "dual":
+        S, H, P = Ds
+        return [opt, torch.optim.SGD(list(H.parameters()) + list(S.parameters()), lr=lr),
+                torch.optim.SGD(list(P.parameters()) + list(S.parameters()), lr=lr)]
+    return [opt, torch.optim.Adam(Ds[0].parameters(), lr=lr)]
+
+
+def _loop_one(a, name):
+    """One loop's wall clock per iteration in this process."""
+    import tempfile
+    import time
+    import adversarial_learning_on_pointclouds_amd as pc
+    from adversarial_learning_on_pointclouds_amd import dataset as D
+    from adversarial_learning_on_pointclouds_amd import trainer
+    from adversarial_learning_on_pointclouds_amd.image_pool import ImagePool
+    B, N, K = 16, 2048, a.iters
+    torch.manual_seed(0)
+    gt = D.DeviceCloudLoader(_synthetic_split(D, D.ShapeNetDatasetGT, a.clouds, N, 0), B,
+                             shuffle=True, seed=1, drop_last=True)
+    ng = D.DeviceCloudLoader(_synthetic_split(D, D.ShapeNetDataset_noGT, a.clouds, N, 1), B,
+                             shuffle=True, seed=2, drop_last=True)
+    G, Ds = _loop_nets(pc, name, N)
+    opts = _loop_opts(name, G, Ds, 1e-5)
+    stamps = []
+
+    def testing(*_a, **_k):  # the test pass, stubbed: a device sync and a time stamp
+        torch.cuda.synchronize()
+        stamps.append(time.perf_counter())
+        return 0.0, 0.0, 0.0, 0.0
+    trainer.run_testing_seg = trainer.run_testing_seg_regulization = testing
+    save0, trainer.torch.save = torch.save, (lambda *_a, **_k: None)  # checkpoints: stubbed
+
+    class Log:
+        n = 0
+        last = ""
+
+        def info(self, s):
+            if s.startswith("iter"):
+                self.n, self.last = self.n + 1, s
+    log = Log()
+    with tempfile.TemporaryDirectory() as tmp:
+        args = argparse.Namespace(device="cuda", total_iterations=2 * K + 1, lambda_seg=1.0,
+                                  lambda_adv=0.01, lambda_disc_shape=1.0, lambda_regu=0.001,
+                                  iter_test_epoch=K, exp_dir=tmp, tensorboard=False, input_pts=N,
+                                  seed=5, use_graph=not a.no_graph)
+        ce = torch.nn.CrossEntropyLoss()
+        head = (gt, ng, enumerate(gt), enumerate(ng), [None], [0] * B, G)
+        tail = (ImagePool(0), ImagePool(0), log, log, None, args)
+        try:
+            if name == "dual":
+                trainer.run_training_seg_dual(*head, *Ds, torch.nn.BCEWithLogitsLoss(), ce, ce,
+                                              *opts, *tail)
+            elif name == "seg":
+                trainer.run_training_seg(*head, Ds[0], torch.nn.BCEWithLogitsLoss(), ce, *opts,
+                                         *tail)
+            elif name == "stack":
+                trainer.run_training_seg_stack(*head, Ds[0], torch.nn.BCELoss(), ce, ce, *opts,
+                                               *tail)
+            else:
+                trainer.run_training_seg_stack_regulization(*head, Ds[0], torch.nn.BCELoss(), ce,
+                                                            torch.nn.MSELoss(), ce, *opts, *tail)
+        finally:
+            trainer.torch.save = save0
+    assert len(stamps) == 3 and log.n == 2 * K + 1, (len(stamps), log.n)
+    graphed = hasattr(trainer, "_SegPairIteration") and not a.no_graph
+    res = {"loop": name, "tree": a.tag, "graphed": graphed, "iters": K, "B": B, "N": N,
+           "clouds": a.clouds, "ms_per_iter": 1e3 * (stamps[2] - stamps[1]) / K,
+           "first_interval_ms_per_iter": 1e3 * (stamps[1] - stamps[0]) / K, "last_line": log.last}
+    if a.step_graphs:
+        res["step_graph_ms"] = _loop_step_graph(pc, name, a)
+    return res
+
+
+def _loop_step_graph(pc, name, a):
+    """The step's own captured graph on resident inputs (what the other modes of
+    this tool time), replayed between device events."""
+    B, N = 16, 2048
+    rng = np.random.default_rng(0)
+    pts, cls, seg = _inputs(rng, 2 * B, N)
+    halves = (pts[:B].contiguous(), cls[:B].contiguous(), seg[:B].contiguous(),
+              pts[B:].contiguous(), cls[B:].contiguous())
+    G, Ds = _loop_nets(pc, name, N)
+    kw = dict(lr=1e-5, lambda_adv=0.01, seed=5)
+    if name == "dual":
+        st = pc.SegDualTrainStep(G, *Ds, lambda_disc_shape=1.0, lr_D_shape=1e-5, lr_D_point=1e-5,
+                                 **kw)
+    elif name == "seg":
+        st = pc.SegAdvTrainStep(G, Ds[0], lr_D=1e-5, **kw)
+    elif name == "stack":
+        st = pc.SegStackTrainStep(G, Ds[0], lr_D=1e-5, lambda_disc_shape=1.0, **kw)
+    else:
+        st = pc.SegStackReguTrainStep(G, Ds[0], lr_D=1e-5, lambda_disc_shape=1.0,
+                                      lambda_regu=0.001, **kw)
+    g = st.capture_on(*halves)
+    _time(g, 5)
+    return statistics.median(_time(g, 20) for _ in range(5))
+
+
+def _loop(a):
+    names = LOOPS if a.loop == "all" else tuple(a.loop.split(","))
+    for n in names:
+        if n not in LOOPS:
+            sys.exit(f"--loop: {n!r} is not one of {LOOPS}")
+    for n in names:
+        line = json.dumps(_loop_one(a, n))
+        print(line, flush=True)
+        if a.jsonl:
+            os.makedirs(os.path.dirname(a.jsonl) or ".", exist_ok=True)
+            with open(a.jsonl, "a") as f:
+                f.write(line + "\n")
+
+
+def _loop_report(a):
+    """profiles/seg_loops_graph_bench.json from the lines of alternated parent /
+    tree processes (round r = the r-th line of each tree for a loop)."""
+    rows = []
+    for path in a.loop_report:
+        with open(path) as f:
+            rows += [json.loads(l) for l in f if l.strip().startswith("{")]
+    out = {"device": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None,
+           "what": "run_training_seg* over two ShapeNet DeviceCloudLoaders (synthetic resident "
+                   "splits), B=16+16 N=2048 fp32, wall-clock ms per iteration over the second of "
+                   "two intervals of `iters` iterations, test pass and checkpoint writes stubbed; "
+                   "parent = the parent commit's loop (eager step, host read per iteration), "
+                   "tree = this tree's graph-fed loop; fresh processes, alternated",
+           "loops": {}}
+    for name in LOOPS:
+        per = {t: [r["ms_per_iter"] for r in rows if r["loop"] == name and r["tree"] == t]
+               for t in ("parent", "tree")}
+        n = min(len(per["parent"]), len(per["tree"]))
+        if not n:
+            continue
+        wins = sum(t < p for p, t in zip(per["parent"][:n], per["tree"][:n]))
+        e = {"rounds": n, "iters": next(r["iters"] for r in rows if r["loop"] == name),
+             "tree_faster_rounds": wins, "graphed_ships": wins * 2 > n}
+        for t in ("parent", "tree"):
+            v = per[t][:n]
+            e[t + "_ms"] = {"median": statistics.median(v), "min": min(v), "max": max(v),
+                            "rounds": v}
+        e["speedup_median"] = e["parent_ms"]["median"] / e["tree_ms"]["median"]
+        sg = [r["step_graph_ms"] for r in rows if r["loop"] == name and "step_graph_ms" in r]
+        if sg:
+            e["step_graph_ms"] = statistics.median(sg)
+        e["tree_graphed"] = all(r["graphed"] for r in rows
+                                if r["loop"] == name and r["tree"] == "tree")
+        out["loops"][name] = e
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: {"parent": v["parent_ms"]["median"], "tree": v["tree_ms"]["median"],
+                          "tree_faster_rounds": v["tree_faster_rounds"], "rounds": v["rounds"],
+                          "step_graph_ms": v.get("step_graph_ms")}
+                      for k, v in out["loops"].items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -503,10 +709,33 @@ def main():
     ap.add_argument("--dual", action="store_true",
                     help="time SegDualTrainStep against the autograd body and the pointwise step "
                          "(profiles/segdual_bench.json)")
+    ap.add_argument("--loop", default=None,
+                    help="time the loops users call: seg, stack, regu, dual (comma-separated) or all")
+    ap.add_argument("--iters", type=int, default=200, help="--loop: iterations per interval")
+    ap.add_argument("--clouds", type=int, default=256, help="--loop: clouds per synthetic split")
+    ap.add_argument("--root", default=None,
+                    help="--loop: import the package from this tree (the parent built into ablib/)")
+    ap.add_argument("--tag", default=None, help="--loop: 'parent' or 'tree' (default: by --root)")
+    ap.add_argument("--no-graph", action="store_true", help="--loop: args.use_graph = False")
+    ap.add_argument("--step-graphs", action="store_true",
+                    help="--loop: also time each step's own captured graph")
+    ap.add_argument("--jsonl", default=None, help="--loop: append the result lines to this file")
+    ap.add_argument("--loop-report", nargs="+", default=None,
+                    help="collected --loop lines -> profiles/seg_loops_graph_bench.json")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.regu and not a.stack:
         ap.error("--regu goes with --stack")
+    if a.loop_report:
+        a.out = a.out or os.path.join("profiles", "seg_loops_graph_bench.json")
+        return _loop_report(a)
+    if a.loop:
+        if not torch.cuda.is_available():
+            sys.exit("segadv_bench: no HIP device (the loops are timed on the MI355X only)")
+        if a.root:  # the other tree's package in front of this one's
+            sys.path.insert(0, os.path.abspath(a.root))
+        a.tag = a.tag or ("parent" if a.root else "tree")
+        return _loop(a)
     if a.out is None:
         a.out = os.path.join("profiles", "segdual_bench.json" if a.dual else
                              "segstack_semi_bench.json" if a.semi and a.stack else
